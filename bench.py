@@ -13,12 +13,138 @@ dist.all_reduce (RCCL over xGMI) while membership/counts run on the moolib
 RPC plane. Weak scaling: per-GPU actor+learner work is fixed as N grows.
 
 One JSON line is printed by rank 0 at the end (driver contract).
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline
+figure needs: set up, warm up, time the N optimizer steps, print the line.
+Everything is seeded (`--seed`): initial weights, env streams and the
+action-sampling generators are the same from run to run. `--full` is where
+measurements beyond the headline belong; none run by default.
+
+`--dump-outputs DIR` lets two builds be compared output for output. The
+training trajectory itself cannot serve for that: sampled actions feed back
+into the observations and the act/learn interleaving follows asynchronous
+completions, so any last-bit difference grows — two runs of ONE build
+differ by 0.4% (relative L2 over all parameters) after 25 optimizer steps
+and by 14% after 220. So after the timed steps the benchmark runs the timed
+path once more as its last step — one actor forward and one learner
+forward+V-trace+loss+backward, the same ImpalaPeer functions at the timed
+shapes — from the seeded initial weights on seeded input batches, and
+writes what that step hands its caller: the actor's policy logits and
+baseline, and the learner's gradient for every parameter, as float32
+DIR/<name>.npy.
 """
 import argparse
+import itertools
 import json
 import os
 import sys
 import time
+
+
+def make_env_factory(num_actions, seed):
+    """Seeded SyntheticAtariEnv factory for EnvPool.
+
+    EnvPool calls the factory inside each forked worker, once per env the
+    worker owns, without telling it which worker it is — so the seed is
+    derived from the per-process call index alone. Envs at the same
+    position in different workers share their reward/done streams and
+    their first frame; their frame sequences part ways with the first
+    sampled actions."""
+    from moolib_amd.envs import SyntheticAtariEnv
+
+    calls = itertools.count()
+
+    def create_env():
+        return SyntheticAtariEnv(
+            num_actions=num_actions,
+            mean_episode_len=1000,
+            seed=(seed * 1000003 + next(calls)) % (2**32),
+        )
+
+    return create_env
+
+
+def snapshot_parameters(peer):
+    """Copies of the (seeded) initial fp32 master parameters."""
+    return [p.detach().clone() for p in peer.model.parameters()]
+
+
+def dump_outputs(peer, cfg, initial_params, seed, out_dir):
+    """Run one last actor forward and learner step of the timed path from
+    `initial_params` on seeded batches and write the results as
+    <out_dir>/<name>.npy (float32). See the module docstring for why the
+    step starts from the initial weights."""
+    import numpy as np
+    import torch
+
+    from moolib_amd.ops import conv3x3
+
+    dev = cfg.device
+    A = cfg.num_actions
+    gen = torch.Generator().manual_seed(seed)
+
+    def env_batch(*lead):
+        # insertion order matches what the engine batches
+        return {
+            "state": torch.randint(0, 256, (*lead, 4, 84, 84), dtype=torch.uint8, generator=gen),
+            "reward": torch.randint(-1, 2, lead, generator=gen).float(),
+            "done": torch.rand(lead, generator=gen) < 0.02,
+            "prev_action": torch.randint(0, A, lead, generator=gen),
+        }
+
+    T1, B = cfg.unroll_length + 1, cfg.batch_size
+    actor_in = env_batch(cfg.actor_batch_size)
+    learn_in = {
+        "env_outputs": env_batch(T1, B),
+        "actor_outputs": {
+            "policy_logits": 0.1 * torch.randn(T1, B, A, generator=gen),
+            "baseline": 0.1 * torch.randn(T1, B, generator=gen),
+            "action": torch.randint(0, A, (T1, B), generator=gen),
+        },
+    }
+
+    def to_dev(n):
+        return {k: to_dev(v) if isinstance(v, dict) else v.to(dev) for k, v in n.items()}
+
+    actor_in, learn_in = to_dev(actor_in), to_dev(learn_in)
+
+    def core_state(batch):
+        ref = next(peer.fwd_model.parameters())
+        return tuple(
+            s.to(device=dev, dtype=ref.dtype) for s in peer.fwd_model.initial_state(batch)
+        )
+
+    if peer.is_cuda:
+        torch.cuda.synchronize()
+    # Back to the initial weights, the way an optimizer step publishes new
+    # ones: master -> bf16 shadow -> packed conv-weight caches.
+    with torch.no_grad():
+        for p, p0 in zip(peer.model.parameters(), initial_params):
+            p.copy_(p0)
+            if p.grad is not None:
+                p.grad.zero_()
+    peer._sync_shadow()
+    if peer.is_cuda and conv3x3.available(16, 16):
+        conv3x3.repack(peer.fwd_model)
+
+    out = {}
+    peer.fwd_model.eval()
+    res = peer._actor_fn({"env": actor_in, "core": core_state(cfg.actor_batch_size)})
+    out["actor.policy_logits"] = res["out"]["policy_logits"]
+    out["actor.baseline"] = res["out"]["baseline"]
+
+    learn_in["initial_core_state"] = core_state(B)
+    peer.compute_gradients(learn_in)
+    for name, p in peer.model.named_parameters():
+        out["learner.grad." + name] = p.grad
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in out.items():
+        a = t.detach().float().cpu().contiguous().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 * 2**20, "dump exceeds 64 MB: %d bytes" % total
 
 
 def run_r2d2(args):
@@ -78,6 +204,21 @@ def main():
     ap.add_argument("--max-seconds", type=float, default=1800.0)
     ap.add_argument("--backend", default=None, help="torch.distributed backend override")
     ap.add_argument("--breakdown", action="store_true", help="print per-phase wall time")
+    ap.add_argument("--seed", type=int, default=0, help="seed for weights, envs and sampling")
+    ap.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, run one last actor forward and learner "
+        "step from the seeded initial weights on seeded batches and write "
+        "their outputs as DIR/<name>.npy (float32)",
+    )
+    ap.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the measurements beyond the headline figure (a plain "
+        "run already does nothing but the headline, so none exist yet)",
+    )
     ap.add_argument(
         "--config",
         default="impala",
@@ -110,11 +251,10 @@ def main():
 
     if os.environ.get("MOOLIB_AMD_LOG"):
         moolib_amd.set_log_level(os.environ["MOOLIB_AMD_LOG"])
-    from moolib_amd.envs import SyntheticAtariEnv
 
     num_actions = 18
     envs = moolib_amd.EnvPool(
-        lambda: SyntheticAtariEnv(num_actions=num_actions, mean_episode_len=1000),
+        make_env_factory(num_actions, args.seed + 7919 * rank),
         num_processes=args.num_actor_cpus,
         batch_size=args.actor_batch_size,
         num_batches=args.num_actor_batches,
@@ -179,13 +319,16 @@ def main():
         group_name="bench",
         lr_schedule=False,
         group_timeout=60.0,  # benchmark ranks never churn; avoid spurious eviction
+        seed=args.seed + 7919 * rank,
     )
+    torch.manual_seed(args.seed)  # initial weights (same on every rank)
     peer = ImpalaPeer(
         cfg,
         envs=envs,
         use_collective_backend=world > 1,
         broker=broker,
     )
+    initial_params = snapshot_parameters(peer) if (rank == 0 and args.dump_outputs) else None
 
     def barrier_sync():
         if dist is not None:
@@ -271,6 +414,9 @@ def main():
         )
         for k, v in sorted(peer.phase_times.items(), key=lambda kv: -kv[1]):
             print("  %-16s %8.3fs  %5.1f%%" % (k, v, 100 * v / elapsed), file=sys.stderr)
+
+    if initial_params is not None:
+        dump_outputs(peer, cfg, initial_params, args.seed, args.dump_outputs)
 
     if rank == 0:
         dtype = "bf16" if (peer.autocast or getattr(peer, "bf16_shadow", False)) else "fp32"

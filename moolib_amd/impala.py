@@ -100,6 +100,8 @@ class ImpalaConfig:
     group_timeout: float = 10.0      # broker eviction / allreduce timeout (seconds)
     bf16_weights: bool = True        # forward on bf16 shadow weights (fp32 master for optimizer/sync):
     #   removes ~250 autocast weight-cast kernels per step from the graph replays (+3.5%)
+    seed: Optional[int] = None       # seed for the action-sampling generators; None draws
+    #   a fresh nondeterministic seed per peer (the default for training)
 
 
 class EnvBatchState:
@@ -338,9 +340,13 @@ class ImpalaPeer:
         self._batch_events = []
         if self.is_cuda and hasattr(self.fwd_model, "sample_generator"):
             self._actor_rng = torch.Generator(device=cfg.device)
-            self._actor_rng.manual_seed(int(torch.seed()) % (2**62))
             self._learn_rng = torch.Generator(device=cfg.device)
-            self._learn_rng.manual_seed(int(torch.seed()) % (2**62))
+            if cfg.seed is None:
+                self._actor_rng.manual_seed(int(torch.seed()) % (2**62))
+                self._learn_rng.manual_seed(int(torch.seed()) % (2**62))
+            else:
+                self._actor_rng.manual_seed(2 * int(cfg.seed) + 1)
+                self._learn_rng.manual_seed(2 * int(cfg.seed) + 2)
         else:
             self._actor_rng = None
             self._learn_rng = None
