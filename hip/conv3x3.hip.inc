@@ -286,6 +286,34 @@ at::Tensor conv3x3_nhwc_fused(at::Tensor x, at::Tensor wPacked, int64_t K,
   const int NB = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   TORCH_CHECK(C == 8 || C == 16 || C == 32, "conv3x3: C in {8,16,32}");
   TORCH_CHECK(K == 16 || K == 32, "conv3x3: K in {16,32}");
+  TORCH_CHECK(epi >= conv3x3::kEpiNone && epi <= conv3x3::kEpiBiasAdd, "conv3x3: epi in 0..3");
+  TORCH_CHECK(rtOverride <= 0 || rtOverride == 1 || rtOverride == 2 || rtOverride == 4,
+              "conv3x3: rt in {1,2,4}");
+  // The kernel indexes every operand from C, K and the output shape alone:
+  // reject anything it would read out of range or reinterpret.
+  auto checkVec = [&](const at::Tensor& t, int64_t n, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == x.device() && t.scalar_type() == at::kBFloat16 &&
+                    t.is_contiguous(),
+                "conv3x3: ", name, " must be a contiguous bf16 tensor on x's device");
+    TORCH_CHECK(t.numel() == n, "conv3x3: ", name, " has ", t.numel(), " elements, expected ", n);
+  };
+  checkVec(wPacked, (int64_t)((9 * C + 31) / 32) * 32 * K, "w_packed");
+  if (biasIn.has_value()) checkVec(*biasIn, C, "bias_in");
+  TORCH_CHECK(epi == conv3x3::kEpiNone || bias1.has_value(), "conv3x3: epi ", epi,
+              " needs bias1");
+  if (bias1.has_value()) checkVec(*bias1, K, "bias1");
+  if (bias2.has_value()) checkVec(*bias2, K, "bias2");
+  TORCH_CHECK(epi != conv3x3::kEpiBiasAdd || res.has_value(), "conv3x3: epi 3 needs res");
+  if (res.has_value()) {
+    TORCH_CHECK(res->is_cuda() && res->device() == x.device() &&
+                    res->scalar_type() == at::kBFloat16,
+                "conv3x3: res must be a bf16 tensor on x's device");
+    TORCH_CHECK(res->dim() == 4 && res->size(0) == NB && res->size(1) == K &&
+                    res->size(2) == H && res->size(3) == W,
+                "conv3x3: res must have the output's shape [N,K,H,W]");
+    TORCH_CHECK(res->is_contiguous(at::MemoryFormat::ChannelsLast),
+                "conv3x3: res channels_last expected");
+  }
   auto out = at::empty({NB, K, H, W},
                        x.options().memory_format(at::MemoryFormat::ChannelsLast));
   const int64_t M = (int64_t)NB * H * W;

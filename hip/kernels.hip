@@ -177,10 +177,15 @@ __global__ void maxpool3x3s2_fwd_kernel(const T* __restrict__ in, T* __restrict_
 
   float best[8];
   int besti[8];
+  // Start at the first IN-BOUNDS tap (tap 0 is padding for the first output
+  // row/column): a window whose values are all -inf never takes the branch
+  // below and must still route its gradient to a real input element, the
+  // first one in scan order like torch.
+  const int firstTap = (oh == 0 ? 3 : 0) + (ow == 0 ? 1 : 0);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     best[j] = -INFINITY;
-    besti[j] = 0;
+    besti[j] = firstTap;
   }
 #pragma unroll
   for (int kh = 0; kh < 3; ++kh) {
@@ -195,7 +200,7 @@ __global__ void maxpool3x3s2_fwd_kernel(const T* __restrict__ in, T* __restrict_
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float v = (float)vin.v[j];
-        if (v > best[j]) {
+        if (v > best[j] || v != v) {  // NaN propagates, as in torch
           best[j] = v;
           besti[j] = kh * 3 + kw;
         }
@@ -396,11 +401,31 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 
 // ------------------------------------------------------------ wrappers
 
+// The LSTM kernels index every operand from T and B alone: each one must be
+// on X's device, contiguous, and of exactly the dtype and shape the kernel
+// reinterprets it as.
+static void checkLstmArg(const at::Tensor& t, const at::Tensor& like, at::ScalarType dtype,
+                         at::IntArrayRef shape, const char* who, const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.device() == like.device(), who, ": ", name,
+              " must be on the same CUDA device as the input");
+  TORCH_CHECK(t.scalar_type() == dtype, who, ": ", name, " must be ", dtype, ", got ",
+              t.scalar_type());
+  TORCH_CHECK(t.sizes() == shape, who, ": ", name, " must have shape ", shape, ", got ",
+              t.sizes());
+  TORCH_CHECK(t.is_contiguous(), who, ": ", name, " must be contiguous");
+}
+
 std::vector<at::Tensor> lstm_fused_fwd(at::Tensor X, at::Tensor notdone, at::Tensor h0,
                                        at::Tensor c0, at::Tensor whhPacked) {
   TORCH_CHECK(X.is_cuda() && X.dtype() == at::kBFloat16 && X.dim() == 3, "lstm fwd: X [T,B,4H] bf16");
+  TORCH_CHECK(X.is_contiguous(), "lstm fwd: X must be contiguous");
   int T = X.size(0), B = X.size(1);
   TORCH_CHECK(X.size(2) == lstm::kG, "lstm fwd: hidden size must be 256");
+  checkLstmArg(notdone, X, at::kFloat, {T, B}, "lstm fwd", "notdone");
+  checkLstmArg(h0, X, at::kBFloat16, {B, lstm::kH}, "lstm fwd", "h0");
+  checkLstmArg(c0, X, at::kFloat, {B, lstm::kH}, "lstm fwd", "c0");
+  checkLstmArg(whhPacked, X, at::kBFloat16, {(int64_t)lstm::kH * lstm::kG}, "lstm fwd",
+               "whhPacked");
   auto opts = X.options();
   auto fopts = opts.dtype(at::kFloat);
   auto H = at::empty({T, B, lstm::kH}, opts);
@@ -424,7 +449,22 @@ std::vector<at::Tensor> lstm_fused_fwd(at::Tensor X, at::Tensor notdone, at::Ten
 std::vector<at::Tensor> lstm_fused_bwd(at::Tensor gates, at::Tensor cs, at::Tensor c0,
                                        at::Tensor notdone, at::Tensor dH, at::Tensor dhT,
                                        at::Tensor dcT, at::Tensor whhPackedN) {
+  TORCH_CHECK(gates.is_cuda() && gates.dtype() == at::kBFloat16 && gates.dim() == 3 &&
+                  gates.size(2) == lstm::kG && gates.is_contiguous(),
+              "lstm bwd: gates [T,B,4H] contiguous bf16");
   int T = gates.size(0), B = gates.size(1);
+  checkLstmArg(cs, gates, at::kFloat, {T, B, lstm::kH}, "lstm bwd", "cs");
+  checkLstmArg(c0, gates, at::kFloat, {B, lstm::kH}, "lstm bwd", "c0");
+  checkLstmArg(notdone, gates, at::kFloat, {T, B}, "lstm bwd", "notdone");
+  checkLstmArg(dH, gates, at::kBFloat16, {T, B, lstm::kH}, "lstm bwd", "dH");
+  // dhT / dcT: an undefined or EMPTY tensor means "no gradient" (the Python
+  // side passes torch.Tensor(), whose data pointer is null)
+  if (dhT.defined() && dhT.numel() > 0)
+    checkLstmArg(dhT, gates, at::kBFloat16, {B, lstm::kH}, "lstm bwd", "dhT");
+  if (dcT.defined() && dcT.numel() > 0)
+    checkLstmArg(dcT, gates, at::kFloat, {B, lstm::kH}, "lstm bwd", "dcT");
+  checkLstmArg(whhPackedN, gates, at::kBFloat16, {(int64_t)lstm::kG * lstm::kH}, "lstm bwd",
+               "whhPackedN");
   auto opts = gates.options();
   auto fopts = opts.dtype(at::kFloat);
   auto dG = at::empty({T, B, lstm::kG}, opts);
@@ -436,8 +476,10 @@ std::vector<at::Tensor> lstm_fused_bwd(at::Tensor gates, at::Tensor cs, at::Tens
                      reinterpret_cast<const lstm::bf16*>(gates.data_ptr()), cs.data_ptr<float>(),
                      c0.data_ptr<float>(), notdone.data_ptr<float>(),
                      reinterpret_cast<const lstm::bf16*>(dH.data_ptr()),
-                     dhT.defined() ? reinterpret_cast<const lstm::bf16*>(dhT.data_ptr()) : nullptr,
-                     dcT.defined() ? dcT.data_ptr<float>() : nullptr,
+                     (dhT.defined() && dhT.numel() > 0)
+                         ? reinterpret_cast<const lstm::bf16*>(dhT.data_ptr())
+                         : nullptr,
+                     (dcT.defined() && dcT.numel() > 0) ? dcT.data_ptr<float>() : nullptr,
                      reinterpret_cast<const lstm::bf16*>(whhPackedN.data_ptr()),
                      reinterpret_cast<lstm::bf16*>(dG.data_ptr()),
                      reinterpret_cast<lstm::bf16*>(dh0.data_ptr()), dc0.data_ptr<float>(), T, B);
@@ -475,8 +517,19 @@ std::vector<at::Tensor> impala_loss(at::Tensor logits, at::Tensor actions,
   auto pc = pg_advantages.contiguous();
   auto vc = vs.contiguous();
   auto bc = baseline.contiguous();
+  TORCH_CHECK(lc.dim() >= 1 && lc.numel() > 0, "loss: non-empty [..., A] logits expected");
   int64_t A = lc.size(-1);
   int64_t N = lc.numel() / A;
+  // the kernel reads one element of each per-row operand for every row
+  auto checkRows = [&](const at::Tensor& t, at::ScalarType dtype, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == lc.device() && t.scalar_type() == dtype,
+                "loss: ", name, " must be a ", dtype, " tensor on the logits' device");
+    TORCH_CHECK(t.numel() == N, "loss: ", name, " has ", t.numel(), " elements, expected ", N);
+  };
+  checkRows(ac, at::kLong, "actions");
+  checkRows(pc, at::kFloat, "pg_advantages");
+  checkRows(vc, at::kFloat, "vs");
+  checkRows(bc, at::kFloat, "baseline");
   auto grad_logits = at::empty_like(lc);
   auto grad_baseline = at::empty_like(bc);
   auto loss_parts = at::zeros({3}, lc.options());
@@ -623,9 +676,12 @@ __global__ void bias_relu_fwd_kernel(const T* __restrict__ x, const T* __restric
 }
 
 // dx = dy * (y > 0); db reduced without contention: a grid-stride loop with
-// stride = blockDim*gridDim (a multiple of c8n, so each thread's channel
-// group is FIXED) accumulates db partials in registers, then one LDS pass
-// and one global atomic per channel per workgroup. The naive
+// stride = blockDim*gridDim accumulates db partials in registers, then one
+// LDS pass and one global atomic per channel per workgroup. Each thread's
+// channel group is FIXED at tid0 % c8n, which is only right if the stride is
+// a multiple of c8n: blockDim (256) covers c8n's power-of-two part and the
+// host rounds gridDim to a multiple of its odd part whenever the loop
+// iterates (channelSumBlocks). The naive
 // one-atomic-per-element version serialized 256 threads onto C addresses
 // and ran 14x slower than bandwidth.
 template <typename T>
@@ -636,7 +692,9 @@ __global__ void bias_relu_bwd_kernel(const T* __restrict__ dy, const T* __restri
   int C = c8n * 8;
   if (threadIdx.x < C) lds_db[threadIdx.x] = 0.f;
   __syncthreads();
-  int64_t stride = (int64_t)blockDim.x * gridDim.x;  // multiple of c8n
+  // a multiple of c8n: blockDim (256) is a multiple of c8n's power-of-two
+  // part, gridDim of its odd part (channelSumBlocks on the host)
+  int64_t stride = (int64_t)blockDim.x * gridDim.x;
   int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int c8 = (int)(tid0 % c8n);
@@ -669,7 +727,9 @@ __global__ void channel_sum_kernel(const T* __restrict__ x, float* __restrict__ 
   int C = c8n * 8;
   if (threadIdx.x < C) lds[threadIdx.x] = 0.f;
   __syncthreads();
-  int64_t stride = (int64_t)blockDim.x * gridDim.x;  // multiple of c8n
+  // a multiple of c8n: blockDim (256) is a multiple of c8n's power-of-two
+  // part, gridDim of its odd part (channelSumBlocks on the host)
+  int64_t stride = (int64_t)blockDim.x * gridDim.x;
   int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int c8 = (int)(tid0 % c8n);
@@ -717,6 +777,20 @@ static void checkNhwcPair(const at::Tensor& x, const char* who) {
   TORCH_CHECK(x.size(1) % 8 == 0, who, ": channels must be a multiple of 8");
 }
 
+// Grid size for the two channel-sum kernels (256 threads). Their threads keep
+// the channel octet tid0 % c8n for the whole grid-stride loop, so the stride
+// 256*blocks must be a multiple of c8n = C/8 (1..8). 256 covers the
+// power-of-two part; when the cap makes the loop iterate, blocks is rounded
+// down to a multiple of c8n's odd part (3, 5 or 7 for C = 24/48, 40, 56).
+// C = 16 and 32 have odd part 1: their launch geometry is untouched.
+static int64_t channelSumBlocks(int64_t total8, int threads, int64_t blockCap, int c8n) {
+  int64_t blocks = std::min<int64_t>((total8 + threads - 1) / threads, blockCap);
+  int64_t odd = c8n;
+  while (odd % 2 == 0) odd /= 2;
+  if (blocks * threads < total8) blocks = std::max<int64_t>(blocks / odd, 1) * odd;
+  return blocks;
+}
+
 at::Tensor bias_relu_fwd(at::Tensor x, at::Tensor b) {
   checkNhwcPair(x, "bias_relu");
   int C = x.size(1);
@@ -737,6 +811,8 @@ at::Tensor bias_relu_fwd(at::Tensor x, at::Tensor b) {
 
 std::vector<at::Tensor> bias_relu_bwd(at::Tensor dy, at::Tensor y) {
   checkNhwcPair(y, "bias_relu_bwd");
+  TORCH_CHECK(dy.is_cuda() && dy.sizes() == y.sizes() && dy.scalar_type() == y.scalar_type(),
+              "bias_relu_bwd: dy must match y in device, shape and dtype");
   auto g = dy.contiguous(at::MemoryFormat::ChannelsLast);
   int C = y.size(1);
   TORCH_CHECK(C <= 64, "bias_relu_bwd: C <= 64 (LDS accumulator)");
@@ -757,7 +833,7 @@ std::vector<at::Tensor> bias_relu_bwd(at::Tensor dy, at::Tensor y) {
   int64_t blockCap = blockCapEnv > 0
                          ? blockCapEnv
                          : std::min<int64_t>(std::max<int64_t>(total8 / 3000, 256), 768);
-  int64_t blocks = std::min<int64_t>((total8 + threads - 1) / threads, blockCap);
+  int64_t blocks = channelSumBlocks(total8, threads, blockCap, C / 8);
   hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::kBFloat16, at::kHalf, y.scalar_type(), "bias_relu_bwd", [&] {
@@ -778,7 +854,7 @@ at::Tensor channel_sum_fp32(at::Tensor x) {
   // small grid: the per-block channel atomics set the floor (see
   // bias_relu_bwd above; same sweep, profiles/evidence/r4j_bias_micro.txt)
   int64_t blockCap = std::min<int64_t>(std::max<int64_t>(total8 / 3000, 256), 768);
-  int64_t blocks = std::min<int64_t>((total8 + threads - 1) / threads, blockCap);
+  int64_t blocks = channelSumBlocks(total8, threads, blockCap, C / 8);
   hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
   AT_DISPATCH_FLOATING_TYPES_AND2(
       at::kBFloat16, at::kHalf, x.scalar_type(), "channel_sum", [&] {

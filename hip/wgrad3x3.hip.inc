@@ -232,7 +232,7 @@ at::Tensor wgrad3x3_nhwc(at::Tensor x, at::Tensor dy) {
   const int WP = (W + 31) & ~31;
   // Largest row-slab R whose LDS fits ~48 KB (leaves room for 2+ workgroups
   // per CU against the 160 KB CDNA4 LDS).
-  int R = 1;
+  int R = 0;
   size_t lds = 0;
   for (int cand : {8, 6, 4, 3, 2, 1}) {
     size_t need = sizeof(uint16_t) * ((size_t)(cand + 2) * C * (WP + 2) + (size_t)cand * K * WP);
@@ -242,6 +242,10 @@ at::Tensor wgrad3x3_nhwc(at::Tensor x, at::Tensor dy) {
       break;
     }
   }
+  // the kernel stages full-width rows: with no slab there is no LDS to run in
+  TORCH_CHECK(R > 0, "wgrad3x3: W=", W, " too wide for C=", C, ", K=", K,
+              " (a one-row slab needs more than 48 KB of LDS)");
+  TORCH_CHECK(NB > 0 && H > 0 && W > 0, "wgrad3x3: empty input");
   const int totalBatches = NB * ((H + R - 1) / R);
   // ~totalBatches/4 capped at 1024 measured best (profiles/evidence/r2l_sweep.txt);
   // fewer blocks also shrink the partial buffer the fold pass reads.

@@ -30,7 +30,7 @@ class _FusedImpalaLoss(torch.autograd.Function):
         k = _kernels()
         parts, glogits, gbaseline = k.impala_loss(
             logits.contiguous(),
-            actions.contiguous(),
+            actions.to(torch.int64).contiguous(),  # any int dtype, like the eager path
             pg_advantages.contiguous(),
             vs.contiguous(),
             baseline.contiguous(),

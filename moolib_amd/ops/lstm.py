@@ -44,9 +44,9 @@ class _FusedLSTMScan(torch.autograd.Function):
         k = _kernels()
         w = w_hh.detach().to(torch.bfloat16)
         packed_t = pack_mfma_b(w.t().contiguous())  # [H, 4H]: K=256, N=1024
-        H, gates, cs, hT, cT = k.lstm_fused_fwd(
-            X.contiguous(), notdone.contiguous(), h0.contiguous(), c0.contiguous(), packed_t
-        )
+        # the kernels take contiguous operands only; the backward reuses these
+        notdone, h0, c0 = notdone.contiguous(), h0.contiguous(), c0.contiguous()
+        H, gates, cs, hT, cT = k.lstm_fused_fwd(X.contiguous(), notdone, h0, c0, packed_t)
         ctx.save_for_backward(gates, cs, c0, notdone, w, h0, H)
         return H, hT, cT
 

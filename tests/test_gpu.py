@@ -199,10 +199,13 @@ class TestFramesKernel:
 
         x = torch.randint(0, 256, (7, 4, 84, 84), dtype=torch.uint8, device="cuda")
         got = _kernels.frames_u8_to_bf16_nhwc(x, 1.0 / 255.0)
-        want = (x.float() / 255.0).bfloat16().contiguous(memory_format=torch.channels_last)
+        # the kernel's own form (multiply by the fp32 scale, round to bf16
+        # once): bit-exact, no tolerance
+        scale = torch.tensor(1.0 / 255.0, dtype=torch.float32, device="cuda")
+        want = (x.float() * scale).bfloat16()
         assert got.dtype == torch.bfloat16
         assert got.is_contiguous(memory_format=torch.channels_last)
-        assert torch.allclose(got.float(), want.float(), atol=1 / 255.0)
+        assert torch.equal(got, want)
 
 
 def _ref_lstm_scan(X, notdone, h0, c0, w_hh):
