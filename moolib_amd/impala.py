@@ -116,7 +116,9 @@ class EnvBatchState:
         self.core_state = tuple(
             s.to(device=device, dtype=dt) for s in model.initial_state(batch_size=B)
         )
-        self.initial_core_state = self.core_state
+        # a copy, never an alias: core_state is updated in place every act,
+        # and the first unroll must be trained from the state it started in
+        self.initial_core_state = tuple(s.clone() for s in self.core_state)
         self.running_reward = torch.zeros(B)
         self.step_count = torch.zeros(B)
         self.time_batcher = moolib_amd.Batcher(cfg.unroll_length + 1, device)
@@ -544,13 +546,16 @@ class ImpalaPeer:
         )
         self.optimizer.step()
         self._sync_shadow()
+        self._repack_conv_weights()
+        return norm
+
+    def _repack_conv_weights(self):
         # Refresh cached MFMA-packed conv weights (ops/conv3x3) so actor
         # graph replays read the updated weights; capturable ops only.
         from moolib_amd.ops import conv3x3 as _c3
 
         if self.is_cuda and _c3.available(16, 16):
             _c3.repack(self.fwd_model)
-        return norm
 
     def step_optimizer(self):
         cfg = self.cfg
@@ -582,6 +587,17 @@ class ImpalaPeer:
             self.scheduler.load_state_dict(state["scheduler"])
         self.model_version = state["model_version"]
 
+    def _adopt_state(self, state):
+        """State-sync branch of step_once: the accumulator has already
+        written the leader's parameters into the master tensors in place."""
+        self.load_state(state)
+        self._sync_shadow()  # master params were replaced by the leader's
+        # The shadow weights receive their data through the flat buffer, so
+        # their version counters do not move, and a captured actor forward
+        # reads the packed buffers without any version check: repack here,
+        # as after an optimizer step.
+        self._repack_conv_weights()
+
     # ----------------------------------------------------------------- loop
 
     def step_once(self):
@@ -596,8 +612,7 @@ class ImpalaPeer:
         if acc.wants_state():
             acc.set_state(self.save_state())
         if acc.has_new_state():
-            self.load_state(acc.state())
-            self._sync_shadow()  # master params were replaced by the leader's
+            self._adopt_state(acc.state())
 
         if not acc.connected():
             time.sleep(0.05)
@@ -775,16 +790,28 @@ class ImpalaPeer:
                     dst.copy_(src, non_blocking=True)
         action = actor_outputs["action"]
         t0 = self._t("act_forward", t0)
+
+        # Stack BEFORE env_state.update: env_outputs["prev_action"] is the
+        # persistent buffer the forward just read, and update() overwrites
+        # it with this step's action. The time batcher must store the value
+        # the actor consumed (a_{t-1}), so both stacks of last_data precede
+        # the overwrite.
+        last_data = {"env_outputs": env_outputs, "actor_outputs": actor_outputs}
+        env_state.time_batcher.stack(last_data)
+        data = None
+        if not env_state.time_batcher.empty():
+            data = env_state.time_batcher.get()
+            # Carry the last entry of the previous unroll into the next one.
+            env_state.time_batcher.stack(last_data)
+        t0 = self._t("act_batch", t0)
+
         env_state.update(cpu_env_outputs, action, self.stats)
         del cpu_env_outputs  # aliases shm; next step() overwrites it
         env_state.future = self.envs.step(cur, action)
         self.stats["env_act_steps"] += action.numel()
         t0 = self._t("act_stats_step", t0)
 
-        last_data = {"env_outputs": env_outputs, "actor_outputs": actor_outputs}
-        env_state.time_batcher.stack(last_data)
-        if not env_state.time_batcher.empty():
-            data = env_state.time_batcher.get()
+        if data is not None:
             data["initial_core_state"] = env_state.initial_core_state
             n_before = self.learn_batcher.size()
             self.learn_batcher.cat(data)
@@ -793,9 +820,7 @@ class ImpalaPeer:
                     ev = torch.cuda.Event()
                     ev.record(self.actor_stream)
                     self._batch_events.append(ev)
-            # Carry the last entry of the previous unroll into the next one.
             env_state.initial_core_state = prev_core_state
-            env_state.time_batcher.stack(last_data)
         if prefetched:
             # all reads of the staged buffers are now issued on this stream;
             # the next prefetch overwrite waits on this event

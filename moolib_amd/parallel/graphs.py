@@ -35,7 +35,8 @@ class GraphedCall:
     call(inputs) runs eagerly until enough warmups have happened, then
     captures and afterwards replays with inputs copied into static buffers.
     Outputs are the static output nest — consumers must copy what they keep
-    before the next call. Falls back to eager permanently if capture fails.
+    before the next call. Falls back to eager permanently if capture fails
+    or an input leaf lives on the host.
     """
 
     def __init__(self, fn, warmup=3, name="graph", generators=()):
@@ -55,6 +56,13 @@ class GraphedCall:
             return self.fn(inputs)
         if self.graph is None:
             try:
+                if any(
+                    isinstance(t, torch.Tensor) and not t.is_cuda
+                    for t in nest.flatten(inputs)
+                ):
+                    # ops on host tensors are not recorded by a capture:
+                    # replays would hand back the capture-time outputs
+                    raise RuntimeError("input leaves on the host")
                 self.static_in = nest.map(
                     lambda t: t.clone() if isinstance(t, torch.Tensor) else t, inputs
                 )
