@@ -1,0 +1,161 @@
+"""R2D2 on the HBM-resident prioritized replay: actor -> replay -> learner.
+
+The same three peers as examples/r2d2_replay.py (a ReplayBuffer served over
+the moolib RPC plane, an actor streaming LSTM rollouts into it, a learner
+sampling prioritized batches), with a real learner: every environment's
+sequence is one replay item that carries the recurrent state at its start,
+the learner (moolib_amd.r2d2.R2D2Learner) computes n-step double-Q TD errors
+with the fused gfx950 loss kernel, and the sequence priorities it returns are
+what goes back into the buffer. On one node, `--ipc` serves samples as hipIpc
+handles (zero-copy GPU->GPU).
+
+Run:  python examples/r2d2.py [--device cuda:0] [--ipc] [--seconds 20]
+"""
+import argparse
+import time
+
+import torch
+
+import moolib_amd
+from moolib_amd.envs import SyntheticAtariEnv
+from moolib_amd.models.atari import AtariNet
+from moolib_amd.r2d2 import R2D2Config, R2D2Learner
+from moolib_amd.replay import ReplayBuffer
+from moolib_amd.utils import nest
+
+SEQUENCE_KEYS = ("state", "reward", "done", "prev_action", "action")
+
+
+def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_envs=32,
+        seconds=20.0, ipc=False, min_replay=None):
+    """Run the workload; returns a metrics dict."""
+    device = device or ("cuda:0" if torch.cuda.is_available() else "cpu")
+    ipc = bool(ipc and str(device).startswith("cuda"))
+    min_replay = batch_size if min_replay is None else min_replay
+
+    # Replay server peer: sequences live in HBM.
+    server_rpc = moolib_amd.Rpc()
+    server_rpc.set_name("replay_server")
+    addr = [a for a in server_rpc.listen("127.0.0.1:0") if a.startswith("tcp://127")][0]
+    buf = ReplayBuffer(capacity, device=device, alpha=0.9, beta=0.6)
+    buf.serve(server_rpc, "replay")
+
+    envs = moolib_amd.EnvPool(
+        lambda: SyntheticAtariEnv(num_actions=18),
+        num_processes=4,
+        batch_size=num_envs,
+        num_batches=1,
+    )
+    learner = R2D2Learner(
+        AtariNet(num_actions=18, use_lstm=True),
+        R2D2Config(burn_in=burn_in, epsilon=0.05),
+        device,
+    )
+    actor_rpc = moolib_amd.Rpc()
+    actor_rpc.set_name("actor")
+    actor_rpc.set_timeout(30)
+    actor_rpc.connect(addr)
+
+    learner_rpc = moolib_amd.Rpc()
+    learner_rpc.set_name("learner")
+    learner_rpc.set_timeout(30)
+    learner_rpc.connect(addr)
+
+    time_batcher = moolib_amd.Batcher(unroll, device)
+    core_state = tuple(s.to(device) for s in learner.online.initial_state(batch_size=num_envs))
+    start_state = core_state  # recurrent state at the start of the current unroll
+    prev_action = torch.zeros(num_envs, dtype=torch.int64, device=device)
+
+    t0 = time.time()
+    frames = sampled = learn_steps = 0
+    add_futures = []
+    metrics = None
+    while time.time() - t0 < seconds:
+        # ---- act (epsilon-greedy on the dueling Q-values) ----
+        obs = envs.step(0, prev_action).result()
+        dev = {k: t.to(device, copy=True) for k, t in obs.items()}
+        dev["prev_action"] = prev_action
+        inputs = {k: dev[k].unsqueeze(0) for k in ("state", "reward", "done", "prev_action")}
+        action, core_state = learner.act(inputs, core_state)
+        action = action.squeeze(0)
+        frames += num_envs
+        time_batcher.stack(dict(
+            state=dev["state"], reward=dev["reward"], done=dev["done"],
+            prev_action=prev_action, action=action,
+        ))
+        prev_action = action
+
+        # ---- feed replay: one item per environment sequence ----
+        if not time_batcher.empty():
+            seq = nest.map(lambda t: t.cpu(), time_batcher.get())  # [T, B, ...]
+            h0, c0 = (s.cpu() for s in start_state)  # [1, B, H]
+            for e in range(num_envs):
+                item = {k: seq[k][:, e].contiguous() for k in SEQUENCE_KEYS}
+                item["core_h"] = h0[:, e].contiguous()
+                item["core_c"] = c0[:, e].contiguous()
+                add_futures.append(actor_rpc.async_("replay_server", "replay.add", item))
+            start_state = core_state
+        add_futures = [f for f in add_futures if not f.done()]
+
+        # ---- learner: prioritized sample, R2D2 step, true TD priorities back ----
+        if len(buf) >= min_replay:
+            fn = "replay.sample_ipc" if ipc else "replay.sample"
+            items, idx, w = learner_rpc.sync("replay_server", fn, batch_size)
+            batch = {k: items[k].transpose(0, 1) for k in SEQUENCE_KEYS}  # time-major views
+            batch["core_state"] = (
+                items["core_h"].transpose(0, 1), items["core_c"].transpose(0, 1)
+            )
+            metrics, priorities = learner.learn(batch, w)
+            learner_rpc.sync("replay_server", "replay.update_priorities", idx, priorities.cpu())
+            sampled += batch_size
+            learn_steps += 1
+
+    dt = time.time() - t0
+    for f in add_futures:
+        f.result()
+    return {
+        "seconds": dt,
+        "frames_acted": frames,
+        "frames_per_s": frames / dt,
+        "buffer_seqs": len(buf),
+        "capacity": capacity,
+        "sampled": sampled,
+        "sampled_per_s": sampled / dt,
+        "learn_steps": learn_steps,
+        "mean_abs_td": float(metrics["mean_abs_td"]) if metrics else float("nan"),
+        "loss": float(metrics["loss"]) if metrics else float("nan"),
+        "unroll": unroll,
+        "burn_in": burn_in,
+        "batch_size": batch_size,
+        "num_envs": num_envs,
+        "ipc": ipc,
+        "device": str(device),
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", default=None)
+    ap.add_argument("--capacity", type=int, default=2048)
+    ap.add_argument("--unroll", type=int, default=40)
+    ap.add_argument("--burn-in", type=int, default=10)
+    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--num-envs", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=20.0)
+    ap.add_argument("--ipc", action="store_true", help="serve samples as hipIpc handles")
+    a = ap.parse_args()
+    m = run(a.device, a.capacity, a.unroll, a.burn_in, a.batch_size, a.num_envs, a.seconds,
+            a.ipc)
+    print(
+        "r2d2: %.1fs, %d frames acted (%.0f/s), buffer %d/%d seqs, %d learner steps, "
+        "%d sequences sampled (%.0f/s), mean |TD| %.4f, loss %.4f"
+        % (
+            m["seconds"], m["frames_acted"], m["frames_per_s"], m["buffer_seqs"],
+            m["capacity"], m["learn_steps"], m["sampled"], m["sampled_per_s"],
+            m["mean_abs_td"], m["loss"],
+        )
+    )
+
+
+if __name__ == "__main__":
+    main()

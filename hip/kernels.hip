@@ -15,11 +15,15 @@
 //     wavefront per row computes softmax/log-softmax via wave reductions
 //     and writes the combined logits gradient directly (saves the autograd
 //     graph + ~15 separate elementwise/softmax kernels of the eager path).
+//   r2d2_loss_kernel (r2d2.hip.inc) — fused R2D2 loss: n-step double-Q
+//     targets under value rescaling, masked sequence loss, sequence
+//     priorities and d(loss)/d(q) in one launch, no atomics.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include <climits>
 #include <cstdlib>
 #include <vector>
 
@@ -398,6 +402,7 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 #include "conv3x3.hip.inc"
 #include "wgrad3x3.hip.inc"
 #include "lstm.hip.inc"
+#include "r2d2.hip.inc"
 
 // ------------------------------------------------------------ wrappers
 
@@ -1186,4 +1191,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_fused_bwd", &lstm_fused_bwd, "fused masked LSTM sequence scan bwd (MFMA, gfx950)");
   m.def("vtrace_from_log_rhos", &vtrace_from_log_rhos, "fused V-trace scan (gfx950)");
   m.def("impala_loss", &impala_loss, "fused IMPALA loss fwd+grad (gfx950)");
+  m.def("r2d2_loss", &r2d2_loss,
+        "fused R2D2 loss: n-step double-Q TD errors, sequence loss, priorities, grad_q (gfx950)",
+        py::arg("q"), py::arg("q_target"), py::arg("actions"), py::arg("rewards"),
+        py::arg("discounts"), py::arg("mask"), py::arg("is_weights"), py::arg("n"),
+        py::arg("eps"), py::arg("rescale"), py::arg("eta"), py::arg("grad_scale"),
+        py::arg("grad_out") = py::none());
+  m.attr("R2D2_MAX_T") = r2d2::kMaxT;  // longest sequence r2d2_loss accepts
 }
