@@ -443,6 +443,19 @@ struct SocketEngine::Impl {
         MRL_LOG_ERROR("epoll_wait failed: %s", strerror(errno));
         break;
       }
+      // Drain the wake eventfd BEFORE taking the queued commands. post()
+      // pushes, then writes the eventfd: drained after the swap, the wake of
+      // a command pushed in between was consumed with its command still
+      // queued, and that command (a send, usually) sat until the 200 ms
+      // epoll timeout. In this order such a wake stays pending and the next
+      // epoll_wait returns at once.
+      for (int i = 0; i < n; ++i) {
+        if (evs[i].data.u64 == 0) {
+          uint64_t junk;
+          while (read(wakeFd, &junk, sizeof(junk)) > 0) {
+          }
+        }
+      }
       // Run queued commands first.
       std::vector<std::function<void()>> batch;
       {
@@ -452,12 +465,7 @@ struct SocketEngine::Impl {
       for (auto& f : batch) f();
       for (int i = 0; i < n; ++i) {
         uint64_t data = evs[i].data.u64;
-        if (data == 0) {  // wake eventfd
-          uint64_t junk;
-          while (read(wakeFd, &junk, sizeof(junk)) > 0) {
-          }
-          continue;
-        }
+        if (data == 0) continue;  // wake eventfd, drained above
         if (data & (uint64_t(1) << 63)) {  // listener
           int lfd = static_cast<int>(data & 0x7fffffff);
           auto lit = listeners.find(lfd);

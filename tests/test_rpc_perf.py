@@ -36,6 +36,27 @@ class TestRpcThroughput:
         print("sync noop: %.0f calls/s (%.2f ms each)" % (rate, 1000 * dt / n))
         assert rate > 300, rate  # loose floor; typical is thousands
 
+    def test_sync_noop_never_waits_for_the_reactor_timeout(self):
+        """A send is a command posted to the reactor thread plus a wake of its
+        eventfd. When the reactor drained the eventfd after taking the queued
+        commands, a command posted in between lost its wake and waited for the
+        200 ms epoll timeout: about one call in a thousand here took 201 ms
+        (and test_sync_noop_rate dropped from 11000 to 900 or 450 calls/s
+        whenever one or two of its 200 calls were hit). 10000 calls expect ten
+        such stalls; one call over 150 ms is granted to a busy machine."""
+        host, client = make_pair()
+        host.define("noop", lambda: None)
+        client.sync("host", "noop")
+        stalls = []
+        for _ in range(10000):
+            t0 = time.perf_counter()
+            client.sync("host", "noop")
+            dt = time.perf_counter() - t0
+            if dt > 0.15:
+                stalls.append(round(dt, 3))
+        print("sync noop: %d of 10000 calls over 150 ms %s" % (len(stalls), stalls[:10]))
+        assert len(stalls) <= 1, stalls
+
     def test_async_noop_pipeline(self):
         host, client = make_pair()
         host.define("noop", lambda: None)
