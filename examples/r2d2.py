@@ -9,7 +9,12 @@ with the fused gfx950 loss kernel, and the sequence priorities it returns are
 what goes back into the buffer. On one node, `--ipc` serves samples as hipIpc
 handles (zero-copy GPU->GPU).
 
-Run:  python examples/r2d2.py [--device cuda:0] [--ipc] [--seconds 20]
+With `--sumtree` the buffer is a SumTreeReplayBuffer (device-side sum tree,
+stratified sampling): every unroll goes in with ONE add_batch(batch_dim=1),
+straight from the device when the buffer lives on the GPU, and samples come
+back time-major, so the learner needs no transposed views.
+
+Run:  python examples/r2d2.py [--device cuda:0] [--ipc] [--sumtree] [--seconds 20]
 """
 import argparse
 import time
@@ -20,14 +25,14 @@ import moolib_amd
 from moolib_amd.envs import SyntheticAtariEnv
 from moolib_amd.models.atari import AtariNet
 from moolib_amd.r2d2 import R2D2Config, R2D2Learner
-from moolib_amd.replay import ReplayBuffer
+from moolib_amd.replay import ReplayBuffer, SumTreeReplayBuffer
 from moolib_amd.utils import nest
 
 SEQUENCE_KEYS = ("state", "reward", "done", "prev_action", "action")
 
 
 def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_envs=32,
-        seconds=20.0, ipc=False, min_replay=None):
+        seconds=20.0, ipc=False, min_replay=None, sumtree=False):
     """Run the workload; returns a metrics dict."""
     device = device or ("cuda:0" if torch.cuda.is_available() else "cpu")
     ipc = bool(ipc and str(device).startswith("cuda"))
@@ -37,7 +42,8 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
     server_rpc = moolib_amd.Rpc()
     server_rpc.set_name("replay_server")
     addr = [a for a in server_rpc.listen("127.0.0.1:0") if a.startswith("tcp://127")][0]
-    buf = ReplayBuffer(capacity, device=device, alpha=0.9, beta=0.6)
+    buffer_cls = SumTreeReplayBuffer if sumtree else ReplayBuffer
+    buf = buffer_cls(capacity, device=device, alpha=0.9, beta=0.6)
     buf.serve(server_rpc, "replay")
 
     envs = moolib_amd.EnvPool(
@@ -86,7 +92,19 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
         prev_action = action
 
         # ---- feed replay: one item per environment sequence ----
-        if not time_batcher.empty():
+        if sumtree and not time_batcher.empty():
+            # the whole [T, B, ...] unroll and its [1, B, H] start state, as they are
+            items = dict(time_batcher.get())
+            items = {k: items[k] for k in SEQUENCE_KEYS}
+            items["core_h"], items["core_c"] = start_state
+            if buf.device.type == "cuda":  # same process, same GPU: no CPU detour
+                buf.add_batch(items, batch_dim=1)
+            else:
+                add_futures.append(
+                    actor_rpc.async_("replay_server", "replay.add_batch", items, None, 1)
+                )
+            start_state = core_state
+        elif not time_batcher.empty():
             seq = nest.map(lambda t: t.cpu(), time_batcher.get())  # [T, B, ...]
             h0, c0 = (s.cpu() for s in start_state)  # [1, B, H]
             for e in range(num_envs):
@@ -100,11 +118,16 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
         # ---- learner: prioritized sample, R2D2 step, true TD priorities back ----
         if len(buf) >= min_replay:
             fn = "replay.sample_ipc" if ipc else "replay.sample"
-            items, idx, w = learner_rpc.sync("replay_server", fn, batch_size)
-            batch = {k: items[k].transpose(0, 1) for k in SEQUENCE_KEYS}  # time-major views
-            batch["core_state"] = (
-                items["core_h"].transpose(0, 1), items["core_c"].transpose(0, 1)
-            )
+            if sumtree:  # time-major from the buffer: [T, B, ...] and [1, B, H]
+                items, idx, w = learner_rpc.sync("replay_server", fn, batch_size, True)
+                batch = {k: items[k] for k in SEQUENCE_KEYS}
+                batch["core_state"] = (items["core_h"], items["core_c"])
+            else:
+                items, idx, w = learner_rpc.sync("replay_server", fn, batch_size)
+                batch = {k: items[k].transpose(0, 1) for k in SEQUENCE_KEYS}  # time-major views
+                batch["core_state"] = (
+                    items["core_h"].transpose(0, 1), items["core_c"].transpose(0, 1)
+                )
             metrics, priorities = learner.learn(batch, w)
             learner_rpc.sync("replay_server", "replay.update_priorities", idx, priorities.cpu())
             sampled += batch_size
@@ -129,6 +152,7 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
         "batch_size": batch_size,
         "num_envs": num_envs,
         "ipc": ipc,
+        "sumtree": bool(sumtree),
         "device": str(device),
     }
 
@@ -143,9 +167,11 @@ def main():
     ap.add_argument("--num-envs", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=20.0)
     ap.add_argument("--ipc", action="store_true", help="serve samples as hipIpc handles")
+    ap.add_argument("--sumtree", action="store_true",
+                    help="SumTreeReplayBuffer: batched adds, stratified time-major samples")
     a = ap.parse_args()
     m = run(a.device, a.capacity, a.unroll, a.burn_in, a.batch_size, a.num_envs, a.seconds,
-            a.ipc)
+            a.ipc, sumtree=a.sumtree)
     print(
         "r2d2: %.1fs, %d frames acted (%.0f/s), buffer %d/%d seqs, %d learner steps, "
         "%d sequences sampled (%.0f/s), mean |TD| %.4f, loss %.4f"

@@ -5,7 +5,11 @@ moolib RPC plane; an actor peer streams LSTM rollout sequences into it; a
 learner peer samples prioritized batches and updates priorities. On one
 node, `--ipc` serves samples as hipIpc handles (zero-copy GPU->GPU).
 
-Run:  python examples/r2d2_replay.py [--device cuda:0] [--ipc] [--seconds 20]
+With `--sumtree` the buffer is a SumTreeReplayBuffer: every unroll becomes
+`num_envs` sequences through one add_batch(batch_dim=1) and samples come back
+time-major.
+
+Run:  python examples/r2d2_replay.py [--device cuda:0] [--ipc] [--sumtree] [--seconds 20]
 """
 import argparse
 import time
@@ -15,12 +19,12 @@ import torch
 import moolib_amd
 from moolib_amd.envs import SyntheticAtariEnv
 from moolib_amd.models.atari import AtariNet
-from moolib_amd.replay import ReplayBuffer
+from moolib_amd.replay import ReplayBuffer, SumTreeReplayBuffer
 from moolib_amd.utils import nest
 
 
 def run(device=None, capacity=2048, unroll=40, batch_size=16, num_envs=32,
-        seconds=20.0, ipc=False):
+        seconds=20.0, ipc=False, sumtree=False):
     """Run the replay workload; returns a metrics dict (also used by
     `bench.py --config r2d2`)."""
     device = device or ("cuda:0" if torch.cuda.is_available() else "cpu")
@@ -35,7 +39,8 @@ def run(device=None, capacity=2048, unroll=40, batch_size=16, num_envs=32,
     server_rpc = moolib_amd.Rpc()
     server_rpc.set_name("replay_server")
     addr = [a for a in server_rpc.listen("127.0.0.1:0") if a.startswith("tcp://127")][0]
-    buf = ReplayBuffer(args.capacity, device=device, alpha=0.6, beta=0.4)
+    buffer_cls = SumTreeReplayBuffer if sumtree else ReplayBuffer
+    buf = buffer_cls(args.capacity, device=device, alpha=0.6, beta=0.4)
     buf.serve(server_rpc, "replay")  # serves .sample and .sample_ipc
 
     # Actor: generate LSTM rollouts from synthetic frames.
@@ -79,7 +84,15 @@ def run(device=None, capacity=2048, unroll=40, batch_size=16, num_envs=32,
             {"state": dev["state"], "action": prev_action, "reward": dev["reward"]}
         )
         # ---- feed replay (sequence-major, one add per unroll) ----
-        if not time_batcher.empty():
+        if sumtree and not time_batcher.empty():
+            seq = dict(time_batcher.get())  # [T, B, ...]: B sequences, one add_batch
+            if buf.device.type == "cuda":  # same process, same GPU: no CPU detour
+                buf.add_batch(seq, batch_dim=1)
+            else:
+                add_futures.append(
+                    actor_rpc.async_("replay_server", "replay.add_batch", seq, None, 1)
+                )
+        elif not time_batcher.empty():
             seq = time_batcher.get()  # [T, B, ...]
             add_futures.append(
                 actor_rpc.async_("replay_server", "replay.add", nest.map(lambda t: t.cpu(), seq))
@@ -90,7 +103,9 @@ def run(device=None, capacity=2048, unroll=40, batch_size=16, num_envs=32,
         # ---- learner: prioritized sample + priority update ----
         if len(buf) >= args.batch_size:
             fn = "replay.sample_ipc" if (args.ipc and device.startswith("cuda")) else "replay.sample"
-            batch, idx, w = learner_rpc.sync("replay_server", fn, args.batch_size)
+            batch, idx, w = learner_rpc.sync(
+                "replay_server", fn, args.batch_size, *((True,) if sumtree else ())
+            )
             td_error = torch.rand(args.batch_size)  # stand-in for the R2D2 TD error
             learner_rpc.sync("replay_server", "replay.update_priorities", idx, td_error)
             sampled += args.batch_size
@@ -108,6 +123,7 @@ def run(device=None, capacity=2048, unroll=40, batch_size=16, num_envs=32,
         "batch_size": args.batch_size,
         "num_envs": args.num_envs,
         "ipc": ipc,
+        "sumtree": bool(sumtree),
         "device": str(device),
     }
 
@@ -121,8 +137,11 @@ def main():
     ap.add_argument("--num-envs", type=int, default=32)
     ap.add_argument("--seconds", type=float, default=20.0)
     ap.add_argument("--ipc", action="store_true", help="serve samples as hipIpc handles")
+    ap.add_argument("--sumtree", action="store_true",
+                    help="SumTreeReplayBuffer: batched adds, stratified time-major samples")
     a = ap.parse_args()
-    m = run(a.device, a.capacity, a.unroll, a.batch_size, a.num_envs, a.seconds, a.ipc)
+    m = run(a.device, a.capacity, a.unroll, a.batch_size, a.num_envs, a.seconds, a.ipc,
+            sumtree=a.sumtree)
     print(
         "r2d2 replay demo: %.1fs, %d frames acted (%.0f/s), buffer %d/%d seqs, "
         "%d sequences sampled (%.0f/s)"

@@ -1048,6 +1048,10 @@ void batched_copy(std::vector<at::Tensor> dsts, std::vector<at::Tensor> srcs) {
   flush();
 }
 
+// Device-side prioritized replay (sum tree + indexed row gather/scatter);
+// uses kMaxCopyDescs above.
+#include "replay.hip.inc"
+
 // ------------------------------------------- batched conv-weight repack
 //
 // The conv3x3 path keeps per-conv MFMA-packed weight buffers (fwd pack +
@@ -1198,4 +1202,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eps"), py::arg("rescale"), py::arg("eta"), py::arg("grad_scale"),
         py::arg("grad_out") = py::none());
   m.attr("R2D2_MAX_T") = r2d2::kMaxT;  // longest sequence r2d2_loss accepts
+  m.def("replay_tree_update", &replay_tree_update,
+        "sum-tree leaves <- priority^alpha (last wins), ancestors, max_priority (gfx950)",
+        py::arg("tree"), py::arg("max_priority"), py::arg("slots"), py::arg("priorities"),
+        py::arg("alpha"), py::arg("L"));
+  m.def("replay_tree_sample", &replay_tree_sample,
+        "stratified sum-tree sample: idx [B], normalised importance weights [B] (gfx950)",
+        py::arg("tree"), py::arg("L"), py::arg("size"), py::arg("u"), py::arg("beta"),
+        py::arg("idx_out") = py::none(), py::arg("weights_out") = py::none());
+  m.def("replay_rows", &replay_rows,
+        "gather / scatter whole items of every nest leaf by a device index, one launch",
+        py::arg("storage"), py::arg("other"), py::arg("index"), py::arg("mode"));
+  m.attr("REPLAY_MAX_UPDATE") = replay::kMaxUpdate;  // slots per replay_tree_update launch
+  m.attr("REPLAY_MAX_SAMPLE") = replay::kMaxSample;  // largest replay_tree_sample batch
 }
