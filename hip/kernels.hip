@@ -1052,6 +1052,9 @@ void batched_copy(std::vector<at::Tensor> dsts, std::vector<at::Tensor> srcs) {
 // uses kMaxCopyDescs above.
 #include "replay.hip.inc"
 
+// Fused flat Adam step: grad norm, clip, update and bf16 shadow in two launches.
+#include "optim.hip.inc"
+
 // ------------------------------------------- batched conv-weight repack
 //
 // The conv3x3 path keeps per-conv MFMA-packed weight buffers (fwd pack +
@@ -1215,4 +1218,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("storage"), py::arg("other"), py::arg("index"), py::arg("mode"));
   m.attr("REPLAY_MAX_UPDATE") = replay::kMaxUpdate;  // slots per replay_tree_update launch
   m.attr("REPLAY_MAX_SAMPLE") = replay::kMaxSample;  // largest replay_tree_sample batch
+  m.def("flat_adam_step", &flat_adam_step,
+        "fused flat Adam: grad norm, clip, update of p/m/v, bf16 shadow; two launches (gfx950)",
+        py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+        py::arg("step"), py::arg("step_next"), py::arg("lr"), py::arg("partial"),
+        py::arg("norm_out"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("max_norm") = py::none());
+  m.attr("FLAT_ADAM_MAX_BLOCKS") = optim::kMaxBlocks;        // grid cap, length of `partial`
+  m.attr("FLAT_ADAM_PASS_ELEMENTS") = optim::kPassElements;  // elements one grid pass covers
 }

@@ -75,6 +75,10 @@ class ImpalaConfig:
     graph_optimizer: bool = True  # hipGraph-capture clip_grad_norm + Adam step
     #   (no autograd in the capture; only used when the LR is constant —
     #   python-float hyperparameters are baked into the graph)
+    fused_optimizer: bool = False  # clip + Adam + bf16 shadow sync as ONE fused
+    #   flat step (optim.FlatAdam: two HIP launches, lr and step counter on
+    #   the device, so an LR schedule no longer rules out graph_optimizer).
+    #   MOOLIB_AMD_FUSED_OPT=1 switches it on.
     graph_learner: bool = False  # hipGraph-capture the learner fwd+bwd.
     #   OFF by default: replays of the captured learner (autograd backward
     #   incl. MIOpen bwd-weight convs) intermittently fault on ROCm 7.0
@@ -235,29 +239,35 @@ class ImpalaPeer:
             num_actions=cfg.num_actions, use_lstm=cfg.use_lstm
         )
         self.model.to(cfg.device)
-        self.optimizer = torch.optim.Adam(
-            self.model.parameters(),
-            lr=cfg.learning_rate,
-            betas=(cfg.adam_beta1, cfg.adam_beta2),
-            eps=cfg.adam_eps,
-            # multi-tensor kernels: one launch per op across all 40 params
-            # instead of 40 tiny latency-bound launches each
-            foreach=True,
-        )
-        if cfg.lr_schedule:
-            factor = cfg.unroll_length * cfg.virtual_batch_size / cfg.total_steps
-            self.scheduler = torch.optim.lr_scheduler.LambdaLR(
-                self.optimizer, lambda epoch: max(1 - epoch * factor, 0)
-            )
-        else:
+        # (read before the other env switches below: it decides which
+        # optimizer is built)
+        if os.environ.get("MOOLIB_AMD_FUSED_OPT", "0") == "1":
+            cfg.fused_optimizer = True
+        if cfg.fused_optimizer:
+            # optim.FlatAdam, built by _build_fused_optimizer once the flat
+            # buffers exist
+            self.optimizer = None
             self.scheduler = None
+        else:
+            self.optimizer = torch.optim.Adam(
+                self.model.parameters(),
+                lr=cfg.learning_rate,
+                betas=(cfg.adam_beta1, cfg.adam_beta2),
+                eps=cfg.adam_eps,
+                # multi-tensor kernels: one launch per op across all 40 params
+                # instead of 40 tiny latency-bound launches each
+                foreach=True,
+            )
+            self.scheduler = self._make_scheduler()
         self._graph_opt = (
             cfg.graph_optimizer
-            and self.scheduler is None
+            # the fused step reads lr from a device scalar: nothing a
+            # schedule changes is baked into its capture
+            and (cfg.fused_optimizer or self.scheduler is None)
             and torch.device(cfg.device).type == "cuda"
             and not os.environ.get("MOOLIB_AMD_NO_OPT_GRAPH")
         )
-        if self._graph_opt:
+        if self._graph_opt and not cfg.fused_optimizer:
             # capturable: the Adam step counter must live on-device so graph
             # replays advance bias correction
             for g in self.optimizer.param_groups:
@@ -333,6 +343,8 @@ class ImpalaPeer:
             self.fwd_model = self.model
             self._master_params = []
             self._fwd_params = []
+        if cfg.fused_optimizer:
+            self._build_fused_optimizer()
         self.env_states = [
             EnvBatchState(cfg, self.fwd_model) for _ in range(cfg.num_actor_batches)
         ]
@@ -417,6 +429,39 @@ class ImpalaPeer:
                 # observation shape differs from the synthetic warm batch
                 logging.warning("prewarm skipped: %s", e)
 
+    def _make_scheduler(self):
+        cfg = self.cfg
+        if not cfg.lr_schedule:
+            return None
+        factor = cfg.unroll_length * cfg.virtual_batch_size / cfg.total_steps
+        return torch.optim.lr_scheduler.LambdaLR(
+            self.optimizer, lambda epoch: max(1 - epoch * factor, 0)
+        )
+
+    def _build_fused_optimizer(self):
+        """cfg.fused_optimizer: FlatAdam over the flat master / grad / shadow
+        buffers this peer already has (bf16-shadow mode), or over flat
+        buffers of its own making otherwise."""
+        from moolib_amd.optim import FlatAdam
+
+        cfg = self.cfg
+        if self.bf16_shadow:
+            params = self._master_params
+            flat = (self._flat_master, self._flat_grad32, self._flat_shadow)
+        else:
+            params = [p for p in self.model.parameters() if p.requires_grad]
+            flat = None
+        self.optimizer = FlatAdam(
+            params,
+            lr=cfg.learning_rate,
+            betas=(cfg.adam_beta1, cfg.adam_beta2),
+            eps=cfg.adam_eps,
+            max_grad_norm=cfg.grad_norm_clipping,
+            shadow_params=self._fwd_params or None,
+            flat=flat,
+        )
+        self.scheduler = self._make_scheduler()
+
     def _prewarm(self):
         """Fill the actor->learner pipeline to its steady backlog at
         construction.
@@ -449,12 +494,13 @@ class ImpalaPeer:
 
     # ------------------------------------------------------------ learning
 
-    def _sync_shadow(self):
+    def _sync_shadow(self, weights=True):
         if not self.bf16_shadow:
             return
         with torch.no_grad():
-            # single cast-copy for ALL params (flat fp32 -> flat bf16)
-            self._flat_shadow.copy_(self._flat_master, non_blocking=True)
+            if weights:
+                # single cast-copy for ALL params (flat fp32 -> flat bf16)
+                self._flat_shadow.copy_(self._flat_master, non_blocking=True)
             bufs_dst = list(self.fwd_model.buffers())
             bufs_src = list(self.model.buffers())
             if bufs_dst:
@@ -541,6 +587,13 @@ class ImpalaPeer:
         return {"out": actor_outputs, "core": core_out if core_out else ()}
 
     def _opt_fn(self, _inputs):
+        if self.cfg.fused_optimizer:
+            # norm, clip, Adam and the bf16 shadow weights in one fused step;
+            # only the buffers are left to copy
+            norm = self.optimizer.step()
+            self._sync_shadow(weights=False)
+            self._repack_conv_weights()
+            return norm
         norm = torch.nn.utils.clip_grad_norm_(
             self.model.parameters(), self.cfg.grad_norm_clipping
         )
@@ -559,6 +612,10 @@ class ImpalaPeer:
 
     def step_optimizer(self):
         cfg = self.cfg
+        if cfg.fused_optimizer:
+            # a replay of the captured step runs no Python: hand the
+            # scheduler's lr to the device scalar here, outside the capture
+            self.optimizer.sync_lr()
         norm = self._opt_call({})
         if self.scheduler is not None:
             self.scheduler.step()
@@ -582,7 +639,20 @@ class ImpalaPeer:
 
     def load_state(self, state):
         # params/buffers were synced by the accumulator already; adopt the rest
-        self.optimizer.load_state_dict(state["optimizer"])
+        # A FlatAdam leader's state says nothing about how an Adam executes
+        # its step (multi-tensor, capturable): keep this peer's own flags.
+        # Adam casts the loaded step counters according to them, so they are
+        # filled in before loading. (A no-op between two peers of one kind.)
+        opt_state = state["optimizer"]
+        opt_state = {
+            "state": opt_state["state"],
+            "param_groups": [
+                dict(g, **{k: mine[k] for k in ("foreach", "capturable")
+                           if k in mine and k not in g})
+                for g, mine in zip(opt_state["param_groups"], self.optimizer.param_groups)
+            ],
+        }
+        self.optimizer.load_state_dict(opt_state)
         if self.scheduler is not None and state.get("scheduler"):
             self.scheduler.load_state_dict(state["scheduler"])
         self.model_version = state["model_version"]

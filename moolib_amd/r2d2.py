@@ -29,6 +29,7 @@ class R2D2Config:
     lr: float = 1e-4
     grad_clip: float = 40.0
     epsilon: float = 0.01  # exploration rate of act()
+    fused_optimizer: bool = False  # clip + Adam as one fused flat step (optim.FlatAdam)
 
 
 class R2D2Learner:
@@ -41,7 +42,17 @@ class R2D2Learner:
         self.target = copy.deepcopy(self.online)
         for p in self.target.parameters():
             p.requires_grad_(False)
-        self.optimizer = torch.optim.Adam(self.online.parameters(), lr=self.config.lr, eps=1e-3)
+        if self.config.fused_optimizer:
+            from moolib_amd.optim import FlatAdam
+
+            self.optimizer = FlatAdam(
+                self.online.parameters(), lr=self.config.lr, eps=1e-3,
+                max_grad_norm=self.config.grad_clip,
+            )
+        else:
+            self.optimizer = torch.optim.Adam(
+                self.online.parameters(), lr=self.config.lr, eps=1e-3
+            )
         # bf16 autocast is what routes AtariNet onto the MFMA kernels
         self.autocast = (self.device.type == "cuda") if autocast is None else bool(autocast)
         self.steps = 0
@@ -114,8 +125,13 @@ class R2D2Learner:
         )
         self.optimizer.zero_grad(set_to_none=True)
         out.loss.backward()
-        grad_norm = torch.nn.utils.clip_grad_norm_(self.online.parameters(), cfg.grad_clip)
-        self.optimizer.step()
+        if cfg.fused_optimizer:
+            # the fused step forms the norm and clips; the norm tensor is the
+            # optimizer's own and the next step overwrites it
+            grad_norm = self.optimizer.step().clone()
+        else:
+            grad_norm = torch.nn.utils.clip_grad_norm_(self.online.parameters(), cfg.grad_clip)
+            self.optimizer.step()
         self.steps += 1
         if self.steps % cfg.target_update_interval == 0:
             self.sync_target()
