@@ -7,14 +7,36 @@ channels, FC 3872->256, one-hot prev action + clipped reward appended,
 optional LSTM(256), policy + baseline heads, multinomial sampling inside
 forward.
 
-MI355X notes: forward runs under bf16 autocast from the IMPALA loop (MFMA
-conv/GEMM via MIOpen/hipBLASLt); the actor path is hipGraph-captured by the
-learner loop (fixed [1, B] shapes), which removes the ~70-kernel launch
-overhead that dominates small-CNN inference.
+MI355X notes: compute is bf16 (autocast over fp32 master weights, or bf16
+shadow weights); the actor path is hipGraph-captured by the learner loop
+(fixed [1, B] shapes), which removes the ~70-kernel launch overhead that
+dominates small-CNN inference. Which kernels the trunk runs is decided per
+call (the MOOLIB_AMD_* switches may change between two forwards):
+
+| stage | condition | route |
+|---|---|---|
+| stem, conv1 | CUDA uint8 frames, bf16 compute, _kernels built, 4 input channels, not NO_CONV1_KERNEL | frames kernel (8-channel pad) + MFMA conv with the bias in the epilogue (`conv3x3.conv1_u8_autograd`; not subject to CONV3_KERNEL), then the section body with no pending bias |
+| stem, frames kernel only | as above but other channel counts or NO_CONV1_KERNEL, and not NO_FRAMES_KERNEL | frames kernel, then section 0 as any other section |
+| stem, eager | all else | `.to(dtype).mul_(1/255)`, channels_last on CUDA, then section 0 |
+| section, fused | `fused_bias.available` | bias-free conv, pool, blocks through `forward_fused` with the conv bias pending |
+| section, plain | otherwise | `nn.Conv2d`, pool, blocks as plain modules |
+| block in `forward_fused` | no grad and `conv3x3.runs_on_mfma` | two fused MFMA conv launches |
+| block in `forward_fused` | otherwise | `bias_relu`/relu, conv, `bias_relu`, conv, `bias_add2` |
+
+A bias-free conv is the MFMA kernel when `conv3x3.runs_on_mfma`, else
+F.conv2d (MIOpen). tests/test_trunk_routes.py pins the launches of each row.
 """
+import os
+
 import torch
 import torch.nn.functional as F
 from torch import nn
+
+from moolib_amd.ops import conv3x3 as c3
+from moolib_amd.ops import fused_bias
+from moolib_amd.ops import lstm as lstm_ops
+from moolib_amd.ops.fused_bias import bias_add2, bias_relu
+from moolib_amd.ops.pool import maxpool3x3s2
 
 
 def _conv3(x, conv):
@@ -22,13 +44,7 @@ def _conv3(x, conv):
     allows (forward AND input-gradient on the custom kernel — measured
     faster than MIOpen at every IMPALA shape, profiles/r2_conv3x3_micro),
     F.conv2d otherwise."""
-    from moolib_amd.ops import conv3x3 as c3
-
-    if (
-        x.is_cuda
-        and c3.available(conv.in_channels, conv.out_channels)
-        and (x.dtype == torch.bfloat16 or torch.is_autocast_enabled())
-    ):
+    if c3.runs_on_mfma(x, conv.in_channels, conv.out_channels):
         return c3.conv3x3_autograd(x, conv)
     return F.conv2d(x, conv.weight, None, padding=1)
 
@@ -54,22 +70,14 @@ class ResidualBlock(nn.Module):
         MFMA conv kernels (ops/conv3x3) — producer relu+bias on load,
         bias+residual on store.
         """
-        from moolib_amd.ops import conv3x3 as c3
-        from moolib_amd.ops.fused_bias import bias_add2, bias_relu
-
         ch = self.conv0.out_channels
-        if (
-            not torch.is_grad_enabled()
-            and x.is_cuda
-            and c3.available(x.size(1), ch)
-            and (x.dtype == torch.bfloat16 or torch.is_autocast_enabled())
-        ):
+        if not torch.is_grad_enabled() and c3.runs_on_mfma(x, x.size(1), ch):
             u = c3.conv3x3(
-                x, c3.packed_buffer(self.conv0), ch,
+                x, c3.packed(self.conv0), ch,
                 relu_in=True, bias_in=pending_bias,
             )
             return c3.conv3x3(
-                u, c3.packed_buffer(self.conv1), ch,
+                u, c3.packed(self.conv1), ch,
                 relu_in=True, bias_in=self.conv0.bias,
                 epi=c3.EPI_BIAS_ADD, bias1=self.conv1.bias,
                 res=x, bias2=pending_bias,
@@ -89,36 +97,26 @@ class ConvSection(nn.Module):
     def __init__(self, in_ch, out_ch):
         super().__init__()
         self.conv = nn.Conv2d(in_ch, out_ch, 3, stride=1, padding=1)
-        self.pool = nn.MaxPool2d(3, stride=2, padding=1)  # CPU fallback
         self.res0 = ResidualBlock(out_ch)
         self.res1 = ResidualBlock(out_ch)
 
     def forward(self, x):
-        from moolib_amd.ops import fused_bias
-        from moolib_amd.ops.pool import maxpool3x3s2
-
         if fused_bias.available(x, self.conv.out_channels):
             # bias-free conv; per-channel bias commutes with the per-channel
             # spatial max, so it rides into res0 as a pending bias.
-            from moolib_amd.ops import conv3x3 as c3
+            return self.after_conv(_conv3(x, self.conv), self.conv.bias)
+        return self.after_conv(self.conv(x), None)
 
-            if (
-                not torch.is_grad_enabled()
-                and c3.available(x.size(1), self.conv.out_channels)
-                and (x.dtype == torch.bfloat16 or torch.is_autocast_enabled())
-            ):
-                u = c3.conv3x3(
-                    x, c3.packed_buffer(self.conv), self.conv.out_channels
-                )
-            else:
-                u = _conv3(x, self.conv)
-            u = maxpool3x3s2(u)
-            u = self.res0.forward_fused(u, self.conv.bias)
+    def after_conv(self, u, pending_bias):
+        """Everything after the section conv: pool, res0, res1. `u` is the
+        conv's output, short of `pending_bias` (a bias the conv left out)
+        unless that is None."""
+        u = maxpool3x3s2(u)
+        if fused_bias.available(u):
+            u = self.res0.forward_fused(u, pending_bias)
             return self.res1.forward_fused(u)
-        x = maxpool3x3s2(self.conv(x))
-        x = self.res0(x)
-        x = self.res1(x)
-        return x
+        assert pending_bias is None
+        return self.res1(self.res0(u))
 
 
 class AtariNet(nn.Module):
@@ -156,63 +154,25 @@ class AtariNet(nn.Module):
             for _ in range(2)
         )
 
-    def forward(self, inputs, core_state=None):
-        x = inputs["state"]
-        reward = inputs["reward"]
-        T, B = x.shape[:2]
-        x = x.flatten(0, 1)
-        import os as _os
-
-        bf16_compute = torch.is_autocast_enabled() or self.fc.weight.dtype == torch.bfloat16
+    def stem(self, x):
+        """Frames [N, C, 84, 84] (uint8 0..255) through section 0."""
+        sec0 = self.sections[0]
         kernels = None
-        if x.is_cuda and x.dtype == torch.uint8 and bf16_compute:
-            try:
-                from moolib_amd import _kernels as kernels
-            except ImportError:
-                kernels = None
-
-        first = 0
+        if x.is_cuda and x.dtype == torch.uint8 and c3.bf16_compute(self.fc.weight):
+            kernels = c3.kernels()
         if (
             kernels is not None
-            and self.sections[0].conv.in_channels == 4
-            and not _os.environ.get("MOOLIB_AMD_NO_CONV1_KERNEL")
+            and sec0.conv.in_channels == 4
+            and not os.environ.get("MOOLIB_AMD_NO_CONV1_KERNEL")
         ):
-            # Fused uint8 frames -> conv1 + bias in one kernel (no separate
-            # preprocessing pass, no 19 MB fp intermediate). Under grad the
-            # same kernel runs through an autograd Function whose backward
-            # is our wgrad kernel + a bias-sum — the first layer never
-            # touches MIOpen in either direction.
-            sec0 = self.sections[0]
-            c1 = sec0.conv
-            from moolib_amd.ops import conv3x3 as c3m
-
-            if torch.is_grad_enabled() and c1.weight.requires_grad:
-                x = c3m.conv1_u8_autograd(x, c1, 1.0 / 255.0)
-            elif _os.environ.get("MOOLIB_AMD_CONV1_SCALAR"):
-                # the original fused scalar kernel (kept for A/Bs)
-                w = c1.weight.detach().to(torch.bfloat16).permute(2, 3, 1, 0).contiguous()
-                b = c1.bias.detach().to(torch.bfloat16)
-                x = kernels.conv1_u8_nhwc(x, w, b, 1.0 / 255.0)
-            else:
-                # same C=8 MFMA route as the learner (graph-capturable:
-                # the packed weights live in a stable version-checked
-                # buffer refreshed by repack())
-                x8 = kernels.frames_u8_to_bf16_nhwc(x, 1.0 / 255.0, 8)
-                x = c3m.conv3x3(
-                    x8, c3m.conv1_packed_buffer(c1), c1.out_channels,
-                    epi=c3m.EPI_BIAS, bias1=c1.bias.detach(),
-                )
-            from moolib_amd.ops.pool import maxpool3x3s2
-
-            x = maxpool3x3s2(x)
-            from moolib_amd.ops import fused_bias
-
-            if fused_bias.available(x):
-                x = sec0.res1.forward_fused(sec0.res0.forward_fused(x))
-            else:
-                x = sec0.res1(sec0.res0(x))
-            first = 1
-        elif kernels is not None and not _os.environ.get("MOOLIB_AMD_NO_FRAMES_KERNEL"):
+            # uint8 frames -> conv1 + bias without a separate preprocessing
+            # pass or a 19 MB fp intermediate. Under grad the same kernels
+            # run through an autograd Function whose backward is our wgrad
+            # kernel + a bias-sum — the first layer never touches MIOpen in
+            # either direction.
+            x = c3.conv1_u8_autograd(x, sec0.conv, 1.0 / 255.0)
+            return sec0.after_conv(x, None)
+        if kernels is not None and not os.environ.get("MOOLIB_AMD_NO_FRAMES_KERNEL"):
             x = kernels.frames_u8_to_bf16_nhwc(x, 1.0 / 255.0)
         else:
             x = x.to(self.fc.weight.dtype).mul_(1.0 / 255.0)
@@ -223,8 +183,14 @@ class AtariNet(nn.Module):
                 # CPU/NCHW path — a self-consistent permutation of learned
                 # features.)
                 x = x.contiguous(memory_format=torch.channels_last)
+        return sec0(x)
 
-        for s in self.sections[first:]:
+    def forward(self, inputs, core_state=None):
+        x = inputs["state"]
+        reward = inputs["reward"]
+        T, B = x.shape[:2]
+        x = self.stem(x.flatten(0, 1))
+        for s in self.sections[1:]:
             x = s(x)
         x = F.relu(x)
         x = x.reshape(T * B, -1)
@@ -239,8 +205,6 @@ class AtariNet(nn.Module):
         if self.use_lstm:
             done = inputs["done"]
             core_input = core_input.view(T, B, -1)
-            from moolib_amd.ops import lstm as lstm_ops
-
             if lstm_ops.available(self.core.hidden_size, core_input.device) and (
                 torch.is_autocast_enabled() or core_input.dtype == torch.bfloat16
             ):

@@ -6,12 +6,16 @@ bias / bias+relu / bias+residual epilogue fused into the store. An IMPALA
 residual block (reference examples/atari/models.py:30-42) becomes two
 kernel launches on the actor. The learner uses `conv3x3_autograd`
 (forward + input-gradient on the same kernel; weight gradient via MIOpen
-wrw by default, our wgrad3x3 kernel opt-in) and `conv1_u8_autograd` for
-the uint8 first layer.
+wrw by default, our wgrad3x3 kernel opt-in); `conv1_u8_autograd` is the
+uint8 first layer of both. `runs_on_mfma` is the one place that decides
+whether a conv takes the kernel, `packed` the one cache of packed weights
+(kinds in PACKERS), refreshed by `repack`.
 """
 import os
 
 import torch
+import torch.nn.functional as F
+from torch import nn
 
 from moolib_amd.ops.lstm import pack_mfma_b
 
@@ -29,6 +33,14 @@ def _k():
     return _kernels
 
 
+def kernels():
+    """moolib_amd._kernels, or None when it is not built."""
+    try:
+        return _k()
+    except ImportError:
+        return None
+
+
 def available(C, K):
     # Default ON for the actor path since r2: with packed weights cached in
     # version-checked persistent buffers (repack() once per optimizer step;
@@ -40,11 +52,20 @@ def available(C, K):
         return False
     if C not in (16, 32) or K not in (16, 32):
         return False
-    try:
-        _k()
-    except ImportError:
-        return False
-    return True
+    return kernels() is not None
+
+
+def bf16_compute(t):
+    """Does the work `t` feeds run in bf16: `t` is bf16 (shadow weights and
+    their activations) or autocast is on (fp32 master weights)."""
+    return t.dtype == torch.bfloat16 or torch.is_autocast_enabled()
+
+
+def runs_on_mfma(x, C, K):
+    """Does a 3x3/s1/p1 conv of `x` from C to K channels run on the MFMA
+    kernel? THE route predicate of the trunk (models/atari.py); evaluated
+    per call, the environment switches may change between two forwards."""
+    return x.is_cuda and available(C, K) and bf16_compute(x)
 
 
 def pack_weight(w):
@@ -62,85 +83,6 @@ def pack_weight(w):
     return pack_mfma_b(gem.to(torch.bfloat16).contiguous())
 
 
-def packed_buffer(conv):
-    """Version-checked persistent packed-weight buffer for an nn.Conv2d.
-
-    Packing costs ~6 small kernels per conv; done inline it dominates the
-    graphed actor forward (measured: the kernel itself BEATS MIOpen at
-    actor shapes in isolation — profiles/r01_conv3x3_micro.txt — but
-    per-replay repacking erased the win). The buffer has a stable address,
-    so hipGraphs may capture reads of it; refresh after weight updates
-    with repack() (graph-capturable: pack + copy_ into the buffer).
-    """
-    w = conv.weight
-    ver = w._version
-    cache = getattr(conv, "_c3_cache", None)
-    if cache is None:
-        conv._c3_cache = cache = [ver, pack_weight(w.detach())]
-        return cache[1]
-    if cache[0] != ver:
-        cache[1].copy_(pack_weight(w.detach()))
-        cache[0] = ver
-    return cache[1]
-
-
-def repack(module):
-    """Refresh every cached packed weight in `module` (call after the
-    optimizer step; safe inside a hipGraph capture).
-
-    On GPU with bf16 weights this is ONE kernel launch for all convs and
-    both directions (repack3x3_batched); the torch-op path (flip/permute/
-    cat per conv, ~14 kernels each) remains the fallback."""
-    import torch.nn as nn
-
-    ws, fs, ds, cps, caches = [], [], [], [], []
-    fallback = []
-    for m in module.modules():
-        if isinstance(m, nn.Conv2d):
-            cache = getattr(m, "_c3_cache", None)
-            dcache = getattr(m, "_c3_dgrad_cache", None)
-            c1cache = getattr(m, "_c1_pack_cache", None)
-            if cache is None and dcache is None and c1cache is None:
-                continue
-            w = m.weight.detach()
-            if w.is_cuda and w.dtype == torch.bfloat16:
-                if cache is not None or dcache is not None:
-                    ws.append(w)
-                    fs.append(cache[1] if cache is not None else w.new_empty(0))
-                    ds.append(dcache[1] if dcache is not None else w.new_empty(0))
-                    cps.append(0)
-                    caches.append((m, cache, dcache))
-                if c1cache is not None:
-                    # the C=8-padded first-conv pack rides the same launch
-                    ws.append(w)
-                    fs.append(c1cache[1])
-                    ds.append(w.new_empty(0))
-                    cps.append(8)
-                    caches.append((m, c1cache, None))
-            else:
-                fallback.append((m, cache, dcache, c1cache))
-    if ws:
-        _k().repack3x3_batched(ws, fs, ds, cps)
-        for m, cache, dcache in caches:
-            if cache is not None:
-                cache[0] = m.weight._version
-            if dcache is not None:
-                dcache[0] = m.weight._version
-    for m, cache, dcache, c1cache in fallback:
-        if cache is not None:
-            cache[1].copy_(pack_weight(m.weight.detach()))
-            cache[0] = m.weight._version
-        if dcache is not None:
-            dcache[1].copy_(pack_weight_dgrad(m.weight.detach()))
-            dcache[0] = m.weight._version
-        if c1cache is not None:
-            import torch.nn.functional as F
-
-            w8 = F.pad(m.weight.detach(), (0, 0, 0, 0, 0, 8 - m.weight.shape[1]))
-            c1cache[1].copy_(pack_weight(w8))
-            c1cache[0] = m.weight._version
-
-
 def pack_weight_dgrad(w):
     """Packed fragments for the INPUT-gradient conv.
 
@@ -151,18 +93,82 @@ def pack_weight_dgrad(w):
     return pack_weight(wd)
 
 
-def dgrad_buffer(conv):
-    """Version-checked persistent dgrad-packed buffer (see packed_buffer)."""
+def pack_weight_c8(w):
+    """C=8 zero-padded pack for the 4-channel first conv.
+
+    The MFMA template's A fragment spans 8 contiguous channels of one
+    tap, so C=4 runs as C=8 with zero channels (25% padded MACs beat the
+    scalar direct conv by a wide margin at learner batch)."""
+    return pack_weight(F.pad(w, (0, 0, 0, 0, 0, 8 - w.shape[1])))
+
+
+# pack kind -> packing function of the nn.Conv2d weight
+PACKERS = {"fwd": pack_weight, "dgrad": pack_weight_dgrad, "c8": pack_weight_c8}
+
+
+def _refresh(entry, kind, w):
+    entry[1].copy_(PACKERS[kind](w.detach()))
+    entry[0] = w._version
+
+
+def packed(conv, kind="fwd"):
+    """Version-checked persistent packed-weight buffer of an nn.Conv2d, of
+    one of the PACKERS kinds; `conv._c3_packs` maps each kind asked for so
+    far to its [weight version, buffer].
+
+    Packing costs ~6 small kernels per conv; done inline it dominates the
+    graphed actor forward (measured: the kernel itself BEATS MIOpen at
+    actor shapes in isolation — profiles/r01_conv3x3_micro.txt — but
+    per-replay repacking erased the win). The buffer has a stable address,
+    so hipGraphs may capture reads of it; refresh after weight updates
+    with repack() (graph-capturable: pack + copy_ into the buffer).
+    """
     w = conv.weight
-    ver = w._version
-    cache = getattr(conv, "_c3_dgrad_cache", None)
-    if cache is None:
-        conv._c3_dgrad_cache = cache = [ver, pack_weight_dgrad(w.detach())]
-        return cache[1]
-    if cache[0] != ver:
-        cache[1].copy_(pack_weight_dgrad(w.detach()))
-        cache[0] = ver
-    return cache[1]
+    packs = conv.__dict__.setdefault("_c3_packs", {})
+    entry = packs.get(kind)
+    if entry is None:
+        packs[kind] = entry = [w._version, PACKERS[kind](w.detach())]
+    elif entry[0] != w._version:
+        _refresh(entry, kind, w)
+    return entry[1]
+
+
+def repack(module):
+    """Refresh every cached packed weight in `module` (call after the
+    optimizer step; safe inside a hipGraph capture).
+
+    On GPU with bf16 weights this is ONE kernel launch for all convs and
+    all kinds (repack3x3_batched, which zero-fills channels >= the real C
+    of a padded pack); the torch-op path (flip/permute/cat per conv, ~14
+    kernels each) remains the fallback."""
+    ws, fs, ds, cps, batched = [], [], [], [], []
+    for m in module.modules():
+        packs = getattr(m, "_c3_packs", None) if isinstance(m, nn.Conv2d) else None
+        if not packs:
+            continue
+        w = m.weight.detach()
+        if not (w.is_cuda and w.dtype == torch.bfloat16):
+            for kind, entry in packs.items():
+                _refresh(entry, kind, m.weight)
+            continue
+        fwd, dgrad, c8 = (packs.get(kind) for kind in ("fwd", "dgrad", "c8"))
+        if fwd is not None or dgrad is not None:
+            ws.append(w)
+            fs.append(fwd[1] if fwd is not None else w.new_empty(0))
+            ds.append(dgrad[1] if dgrad is not None else w.new_empty(0))
+            cps.append(0)
+        if c8 is not None:
+            # the C=8-padded first-conv pack rides the same launch
+            ws.append(w)
+            fs.append(c8[1])
+            ds.append(w.new_empty(0))
+            cps.append(8)
+        batched.append(m)
+    if ws:
+        _k().repack3x3_batched(ws, fs, ds, cps)
+        for m in batched:
+            for entry in m._c3_packs.values():
+                entry[0] = m.weight._version
 
 
 class _Conv3x3Fn(torch.autograd.Function):
@@ -175,7 +181,7 @@ class _Conv3x3Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, conv_module):
         xb = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        y = conv3x3(xb, packed_buffer(conv_module), weight.shape[0])
+        y = conv3x3(xb, packed(conv_module), weight.shape[0])
         ctx.save_for_backward(xb, weight)
         ctx.conv_module = conv_module
         ctx.x_dtype = x.dtype
@@ -188,7 +194,7 @@ class _Conv3x3Fn(torch.autograd.Function):
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            dx = conv3x3(dy, dgrad_buffer(m), w.shape[1])
+            dx = conv3x3(dy, packed(m, "dgrad"), w.shape[1])
             if dx.dtype != ctx.x_dtype:
                 dx = dx.to(ctx.x_dtype)
         if ctx.needs_input_grad[1]:
@@ -222,47 +228,28 @@ def conv3x3_autograd(x, conv_module):
     return _Conv3x3Fn.apply(x, conv_module.weight, conv_module)
 
 
-def conv1_packed_buffer(conv):
-    """C=8 zero-padded MFMA pack for the 4-channel first conv.
-
-    The MFMA template's A fragment spans 8 contiguous channels of one
-    tap, so C=4 runs as C=8 with zero channels (25% padded MACs beat the
-    scalar direct conv by a wide margin at learner batch). Version-checked
-    like packed_buffer; refreshed by repack() (the batched repack kernel
-    zero-fills channels >= the real C)."""
-    import torch.nn.functional as F
-
-    w = conv.weight
-    ver = w._version
-    cache = getattr(conv, "_c1_pack_cache", None)
-    if cache is None or cache[0] != ver:
-        w8 = F.pad(w.detach(), (0, 0, 0, 0, 0, 8 - w.shape[1]))
-        packed = pack_weight(w8)
-        if cache is None:
-            conv._c1_pack_cache = cache = [ver, packed]
-        else:
-            cache[1].copy_(packed)
-            cache[0] = ver
-    return cache[1]
+def _conv1_u8(x_u8, conv, scale):
+    """First conv (uint8 frames -> 16ch) on every route: frames decode to
+    a C=8 zero-padded bf16 NHWC tensor (one fused kernel) and the conv runs
+    on the MFMA template with the bias fused into the epilogue. Graph-
+    capturable: the packed weights live in a stable version-checked buffer
+    refreshed by repack(). Returns (padded activation, output)."""
+    xb8 = _k().frames_u8_to_bf16_nhwc(x_u8, scale, 8)
+    y = conv3x3(
+        xb8, packed(conv, "c8"), conv.out_channels,
+        epi=EPI_BIAS, bias1=conv.bias.detach(),
+    )
+    return xb8, y
 
 
 class _Conv1U8Fn(torch.autograd.Function):
-    """First conv (uint8 frames -> 16ch), learner path: frames decode to a
-    C=8 zero-padded bf16 NHWC tensor (one fused kernel) and the conv runs
-    on the MFMA template with the bias fused into the epilogue; dW comes
-    from our wgrad kernel on the saved padded activation, db is a sum.
-    No MIOpen anywhere in the layer (frames never need an input
-    gradient). The scalar conv1_u8 kernel remains the actor (no-grad,
-    hipGraph-captured) path where N is small."""
+    """_conv1_u8 under autograd: dW comes from our wgrad kernel on the
+    saved padded activation, db is a sum. No MIOpen anywhere in the layer
+    (frames never need an input gradient)."""
 
     @staticmethod
     def forward(ctx, x_u8, weight, bias, conv_module, scale):
-        k = _k()
-        xb8 = k.frames_u8_to_bf16_nhwc(x_u8, scale, 8)
-        y = conv3x3(
-            xb8, conv1_packed_buffer(conv_module), weight.shape[0],
-            epi=EPI_BIAS, bias1=bias.detach(),
-        )
+        xb8, y = _conv1_u8(x_u8, conv_module, scale)
         ctx.save_for_backward(xb8, weight)
         return y
 
@@ -280,9 +267,14 @@ class _Conv1U8Fn(torch.autograd.Function):
 
 
 def conv1_u8_autograd(x_u8, conv_module, scale):
-    return _Conv1U8Fn.apply(
-        x_u8, conv_module.weight, conv_module.bias, conv_module, scale
-    )
+    """The uint8 first conv of actor and learner alike. Without grad or
+    with a frozen weight the two launches are made directly (a trainable
+    bias alone must not pull in the wgrad kernel)."""
+    if torch.is_grad_enabled() and conv_module.weight.requires_grad:
+        return _Conv1U8Fn.apply(
+            x_u8, conv_module.weight, conv_module.bias, conv_module, scale
+        )
+    return _conv1_u8(x_u8, conv_module, scale)[1]
 
 
 def conv3x3(x, w_packed, k, relu_in=False, bias_in=None, epi=EPI_NONE,

@@ -515,9 +515,9 @@ class TestTrunkIntegerExact:
         model = build_model(params, mode)
         run_model(model, mode, int_inputs(frames), grads={"trunk": G})
         run_model(model, mode, int_inputs(frames), no_grad=True)
-        assert hasattr(model.sections[0].conv, "_c1_pack_cache")
+        assert "c8" in model.sections[0].conv._c3_packs
         for conv in (model.sections[1].conv, model.sections[2].res1.conv1):
-            assert hasattr(conv, "_c3_cache") and hasattr(conv, "_c3_dgrad_cache")
+            assert "fwd" in conv._c3_packs and "dgrad" in conv._c3_packs
         params, frames, G = int_case(INT_SEEDS[1])
         with torch.no_grad():
             for k, p in model.named_parameters():
