@@ -14,7 +14,11 @@ stratified sampling): every unroll goes in with ONE add_batch(batch_dim=1),
 straight from the device when the buffer lives on the GPU, and samples come
 back time-major, so the learner needs no transposed views.
 
-Run:  python examples/r2d2.py [--device cuda:0] [--ipc] [--sumtree] [--seconds 20]
+With `--fused-act` the actor's head is the fused epsilon-greedy kernel
+(ops.act), and each of the `num_envs` environments explores at its own
+epsilon of the Ape-X ladder.
+
+Run:  python examples/r2d2.py [--device cuda:0] [--ipc] [--sumtree] [--fused-act] [--seconds 20]
 """
 import argparse
 import time
@@ -24,6 +28,7 @@ import torch
 import moolib_amd
 from moolib_amd.envs import SyntheticAtariEnv
 from moolib_amd.models.atari import AtariNet
+from moolib_amd.ops.act import epsilon_ladder
 from moolib_amd.r2d2 import R2D2Config, R2D2Learner
 from moolib_amd.replay import ReplayBuffer, SumTreeReplayBuffer
 from moolib_amd.utils import nest
@@ -32,7 +37,7 @@ SEQUENCE_KEYS = ("state", "reward", "done", "prev_action", "action")
 
 
 def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_envs=32,
-        seconds=20.0, ipc=False, min_replay=None, sumtree=False):
+        seconds=20.0, ipc=False, min_replay=None, sumtree=False, fused_act=False):
     """Run the workload; returns a metrics dict."""
     device = device or ("cuda:0" if torch.cuda.is_available() else "cpu")
     ipc = bool(ipc and str(device).startswith("cuda"))
@@ -54,9 +59,11 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
     )
     learner = R2D2Learner(
         AtariNet(num_actions=18, use_lstm=True),
-        R2D2Config(burn_in=burn_in, epsilon=0.05),
+        R2D2Config(burn_in=burn_in, epsilon=0.05, fused_act=fused_act),
         device,
     )
+    # the Ape-X ladder: every environment explores at its own rate
+    epsilon = epsilon_ladder(num_envs).to(device) if fused_act else None
     actor_rpc = moolib_amd.Rpc()
     actor_rpc.set_name("actor")
     actor_rpc.set_timeout(30)
@@ -82,7 +89,7 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
         dev = {k: t.to(device, copy=True) for k, t in obs.items()}
         dev["prev_action"] = prev_action
         inputs = {k: dev[k].unsqueeze(0) for k in ("state", "reward", "done", "prev_action")}
-        action, core_state = learner.act(inputs, core_state)
+        action, core_state = learner.act(inputs, core_state, epsilon=epsilon)
         action = action.squeeze(0)
         frames += num_envs
         time_batcher.stack(dict(
@@ -153,6 +160,7 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
         "num_envs": num_envs,
         "ipc": ipc,
         "sumtree": bool(sumtree),
+        "fused_act": bool(fused_act),
         "device": str(device),
     }
 
@@ -169,9 +177,11 @@ def main():
     ap.add_argument("--ipc", action="store_true", help="serve samples as hipIpc handles")
     ap.add_argument("--sumtree", action="store_true",
                     help="SumTreeReplayBuffer: batched adds, stratified time-major samples")
+    ap.add_argument("--fused-act", action="store_true",
+                    help="fused epsilon-greedy head, one epsilon_ladder epsilon per environment")
     a = ap.parse_args()
     m = run(a.device, a.capacity, a.unroll, a.burn_in, a.batch_size, a.num_envs, a.seconds,
-            a.ipc, sumtree=a.sumtree)
+            a.ipc, sumtree=a.sumtree, fused_act=a.fused_act)
     print(
         "r2d2: %.1fs, %d frames acted (%.0f/s), buffer %d/%d seqs, %d learner steps, "
         "%d sequences sampled (%.0f/s), mean |TD| %.4f, loss %.4f"

@@ -18,6 +18,9 @@
 //   r2d2_loss_kernel (r2d2.hip.inc) — fused R2D2 loss: n-step double-Q
 //     targets under value rescaling, masked sequence loss, sequence
 //     priorities and d(loss)/d(q) in one launch, no atomics.
+//   act_categorical_kernel, act_eps_greedy_kernel (act.hip.inc) — the actor's
+//     action head: Philox4x32-10 sampling from a [seed, step] state on the
+//     device, one launch each.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
@@ -1052,6 +1055,9 @@ void batched_copy(std::vector<at::Tensor> dsts, std::vector<at::Tensor> srcs) {
 // uses kMaxCopyDescs above.
 #include "replay.hip.inc"
 
+// Fused actor head: Philox categorical sampling and epsilon-greedy dueling Q.
+#include "act.hip.inc"
+
 // Fused flat Adam step: grad norm, clip, update and bf16 shadow in two launches.
 #include "optim.hip.inc"
 
@@ -1218,6 +1224,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("storage"), py::arg("other"), py::arg("index"), py::arg("mode"));
   m.attr("REPLAY_MAX_UPDATE") = replay::kMaxUpdate;  // slots per replay_tree_update launch
   m.attr("REPLAY_MAX_SAMPLE") = replay::kMaxSample;  // largest replay_tree_sample batch
+  m.def("act_categorical", &act_categorical,
+        "action ~ softmax(logits) from [seed, step] Philox state or explicit uniforms (gfx950)",
+        py::arg("logits"), py::arg("state") = py::none(), py::arg("u") = py::none(),
+        py::arg("action_out") = py::none());
+  m.def("act_eps_greedy", &act_eps_greedy,
+        "epsilon-greedy dueling head: action, q_taken, q_max in one launch (gfx950)",
+        py::arg("value"), py::arg("advantage"), py::arg("epsilon"), py::arg("state") = py::none(),
+        py::arg("u") = py::none(), py::arg("action_out") = py::none(),
+        py::arg("q_taken_out") = py::none(), py::arg("q_max_out") = py::none());
+  m.attr("ACT_MAX_ACTIONS") = act::kMaxActions;  // widest row the act kernels accept
   m.def("flat_adam_step", &flat_adam_step,
         "fused flat Adam: grad norm, clip, update of p/m/v, bf16 shadow; two launches (gfx950)",
         py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),

@@ -79,6 +79,11 @@ class ImpalaConfig:
     #   flat step (optim.FlatAdam: two HIP launches, lr and step counter on
     #   the device, so an LR schedule no longer rules out graph_optimizer).
     #   MOOLIB_AMD_FUSED_OPT=1 switches it on.
+    fused_sampling: bool = False  # sample the actor's actions with the fused
+    #   Philox head (ops.act.sample_categorical: one HIP launch, its [seed,
+    #   step] state on the device) instead of torch.multinomial on a torch
+    #   generator, so the captured actor graph registers no generator.
+    #   MOOLIB_AMD_FUSED_SAMPLING=1 switches it on.
     graph_learner: bool = False  # hipGraph-capture the learner fwd+bwd.
     #   OFF by default: replays of the captured learner (autograd backward
     #   incl. MIOpen bwd-weight convs) intermittently fault on ROCm 7.0
@@ -243,6 +248,8 @@ class ImpalaPeer:
         # optimizer is built)
         if os.environ.get("MOOLIB_AMD_FUSED_OPT", "0") == "1":
             cfg.fused_optimizer = True
+        if os.environ.get("MOOLIB_AMD_FUSED_SAMPLING", "0") == "1":
+            cfg.fused_sampling = True
         if cfg.fused_optimizer:
             # optim.FlatAdam, built by _build_fused_optimizer once the flat
             # buffers exist
@@ -352,7 +359,22 @@ class ImpalaPeer:
             torch.cuda.Stream() if (self.is_cuda and cfg.actor_side_stream) else None
         )
         self._batch_events = []
-        if self.is_cuda and hasattr(self.fwd_model, "sample_generator"):
+        self._actor_sampler = None
+        self._learn_sampler = None
+        if self.is_cuda and cfg.fused_sampling and hasattr(self.fwd_model, "sampler_state"):
+            # one [seed, step] state where there would be a generator: a
+            # replay advances it on the device, nothing to register
+            from moolib_amd.ops import act as act_ops
+
+            if cfg.seed is None:
+                seeds = [int(torch.seed()) % (2**62) for _ in range(2)]
+            else:
+                seeds = [2 * int(cfg.seed) + 1, 2 * int(cfg.seed) + 2]
+            self._actor_sampler = act_ops.new_state(seeds[0], cfg.device)
+            self._learn_sampler = act_ops.new_state(seeds[1], cfg.device)
+            self._actor_rng = None
+            self._learn_rng = None
+        elif self.is_cuda and hasattr(self.fwd_model, "sample_generator"):
             self._actor_rng = torch.Generator(device=cfg.device)
             self._learn_rng = torch.Generator(device=cfg.device)
             if cfg.seed is None:
@@ -513,6 +535,9 @@ class ImpalaPeer:
         model = self.fwd_model
         if self._learn_rng is not None:
             model.sample_generator = self._learn_rng
+        sampler = getattr(self, "_learn_sampler", None)
+        if sampler is not None:
+            model.sampler_state = sampler
         # (shadow-grad zeroing happens in compute_gradients, outside any
         # captured region, as ONE foreach launch)
         env_outputs = data["env_outputs"]
@@ -578,6 +603,11 @@ class ImpalaPeer:
         env_outputs, core_state = inputs["env"], inputs["core"]
         if self._actor_rng is not None:
             self.fwd_model.sample_generator = self._actor_rng
+        # (getattr: callers that drive this function with a stand-in for the
+        # peer know only fwd_model, autocast and _actor_rng)
+        sampler = getattr(self, "_actor_sampler", None)
+        if sampler is not None:
+            self.fwd_model.sampler_state = sampler
         with torch.no_grad(), torch.autocast(
             "cuda", dtype=torch.bfloat16, enabled=self.autocast, cache_enabled=False
         ):

@@ -32,6 +32,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from moolib_amd.ops import act as act_ops
 from moolib_amd.ops import conv3x3 as c3
 from moolib_amd.ops import fused_bias
 from moolib_amd.ops import lstm as lstm_ops
@@ -145,6 +146,10 @@ class AtariNet(nn.Module):
         # state is what forced the actor side stream off; per-capture
         # generators make concurrent replays sound.
         self.sample_generator = None
+        # Optional [seed, step] state of ops.act (int64 [2] on the device):
+        # when set, CUDA logits are sampled by the fused Philox head, one
+        # launch and no torch generator at all.
+        self.sampler_state = None
 
     def initial_state(self, batch_size=1):
         if not self.use_lstm:
@@ -250,10 +255,15 @@ class AtariNet(nn.Module):
             # trains on the ACTOR's actions), and multinomial is one of
             # the slowest ops in the step (~230 us CPU+GPU at [672, 18]) —
             # skip it whenever autograd is recording.
-            action = torch.multinomial(
-                F.softmax(policy_logits, dim=-1), num_samples=1,
-                generator=self.sample_generator,
-            )
+            if self.sampler_state is not None and policy_logits.is_cuda:
+                action = act_ops.sample_categorical(
+                    policy_logits.view(T * B, self.num_actions), state=self.sampler_state
+                )
+            else:
+                action = torch.multinomial(
+                    F.softmax(policy_logits, dim=-1), num_samples=1,
+                    generator=self.sample_generator,
+                )
             out["action"] = action.view(T, B)
         return out, core_state
 

@@ -15,6 +15,7 @@ import dataclasses
 
 import torch
 
+from moolib_amd.ops import act as act_ops
 from moolib_amd.ops.r2d2 import dueling_q, r2d2_loss
 
 
@@ -30,6 +31,8 @@ class R2D2Config:
     grad_clip: float = 40.0
     epsilon: float = 0.01  # exploration rate of act()
     fused_optimizer: bool = False  # clip + Adam as one fused flat step (optim.FlatAdam)
+    fused_act: bool = False  # act() head as one fused launch (ops.act.epsilon_greedy_dueling)
+    seed: int = None  # of the fused act head's sampler state; None takes a fresh one
 
 
 class R2D2Learner:
@@ -56,6 +59,13 @@ class R2D2Learner:
         # bf16 autocast is what routes AtariNet onto the MFMA kernels
         self.autocast = (self.device.type == "cuda") if autocast is None else bool(autocast)
         self.steps = 0
+        # [seed, step] of the fused act head; lives with the model
+        self.act_state = None
+        if self.config.fused_act:
+            seed = self.config.seed
+            if seed is None:
+                seed = int(torch.seed()) % (2**62)
+            self.act_state = act_ops.new_state(seed, self.device)
 
     def _amp(self):
         if self.autocast:
@@ -68,15 +78,40 @@ class R2D2Learner:
         return dueling_q(out["baseline"].float(), out["policy_logits"].float()), core_state
 
     @torch.no_grad()
-    def act(self, inputs, core_state):
+    def act(self, inputs, core_state, epsilon=None, return_q=False):
         """epsilon-greedy actions [T,B] for time-major `inputs`, and the new
-        core state."""
+        core state.
+
+        `epsilon`, a float32 [B] tensor of one exploration rate per
+        environment, overrides config.epsilon. With `return_q` the result is
+        (action, core_state, (q_taken, q_max)): the Q-values of the actions
+        taken and of the greedy ones, each [T,B]. With config.fused_act the
+        whole head is one launch of ops.act.epsilon_greedy_dueling driven by
+        the learner's own sampler state, and no torch generator is used.
+        """
+        if self.config.fused_act:
+            with self._amp():
+                out, core_state = self.online(inputs, core_state)
+            value = out["baseline"].float()
+            eps = self.config.epsilon if epsilon is None else (
+                epsilon.to(value.device).expand(value.shape)
+            )
+            action, q_taken, q_max = act_ops.epsilon_greedy_dueling(
+                value, out["policy_logits"].float(), eps, state=self.act_state
+            )
+            if return_q:
+                return action, core_state, (q_taken, q_max)
+            return action, core_state
         q, core_state = self._q_values(self.online, inputs, core_state)
-        action = q.argmax(dim=-1)
-        if self.config.epsilon > 0:
-            explore = torch.rand(action.shape, device=action.device) < self.config.epsilon
+        greedy = action = q.argmax(dim=-1)
+        if epsilon is not None or self.config.epsilon > 0:
+            eps = self.config.epsilon if epsilon is None else epsilon.to(action.device)
+            explore = torch.rand(action.shape, device=action.device) < eps
             random_action = torch.randint_like(action, q.shape[-1])
             action = torch.where(explore, random_action, action)
+        if return_q:
+            taken = q.gather(-1, action.unsqueeze(-1)).squeeze(-1)
+            return action, core_state, (taken, q.gather(-1, greedy.unsqueeze(-1)).squeeze(-1))
         return action, core_state
 
     def sync_target(self):
