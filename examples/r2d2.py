@@ -18,7 +18,15 @@ With `--fused-act` the actor's head is the fused epsilon-greedy kernel
 (ops.act), and each of the `num_envs` environments explores at its own
 epsilon of the Ape-X ladder.
 
-Run:  python examples/r2d2.py [--device cuda:0] [--ipc] [--sumtree] [--fused-act] [--seconds 20]
+With `--period N` the sequences overlap: one starts every N steps (R2D2 uses
+half the unroll), each with the recurrent state at its own start. With
+`--actor-priorities` every new sequence enters the buffer at the n-step TD
+priority the actor computes from its own Q-values (ops.r2d2.actor_priorities,
+one launch), not at the highest priority seen. Either flag routes the actor
+through moolib_amd.r2d2.SequenceBuilder.
+
+Run:  python examples/r2d2.py [--device cuda:0] [--ipc] [--sumtree] [--fused-act]
+                              [--period 20] [--actor-priorities] [--seconds 20]
 """
 import argparse
 import time
@@ -36,8 +44,28 @@ from moolib_amd.utils import nest
 SEQUENCE_KEYS = ("state", "reward", "done", "prev_action", "action")
 
 
+def _add_sequences(buf, actor_rpc, sumtree, items, priorities):
+    """Feed what a SequenceBuilder emitted ([T, B, ...] leaves, core_h / core_c
+    [1, B, H], priorities [B] or None) to the replay; returns the RPC futures."""
+    if sumtree:
+        if buf.device.type == "cuda":  # same process, same GPU: no CPU detour
+            buf.add_batch(items, priorities, batch_dim=1)
+            return []
+        return [actor_rpc.async_("replay_server", "replay.add_batch", items, priorities, 1)]
+    seq = nest.map(lambda t: t.cpu(), items)
+    priorities = None if priorities is None else priorities.cpu().tolist()
+    futures = []
+    for e in range(seq["reward"].shape[1]):
+        item = {k: seq[k][:, e].contiguous() for k in SEQUENCE_KEYS + ("core_h", "core_c")}
+        futures.append(actor_rpc.async_(
+            "replay_server", "replay.add", item, None if priorities is None else priorities[e]
+        ))
+    return futures
+
+
 def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_envs=32,
-        seconds=20.0, ipc=False, min_replay=None, sumtree=False, fused_act=False):
+        seconds=20.0, ipc=False, min_replay=None, sumtree=False, fused_act=False,
+        period=None, actor_priorities=False):
     """Run the workload; returns a metrics dict."""
     device = device or ("cuda:0" if torch.cuda.is_available() else "cpu")
     ipc = bool(ipc and str(device).startswith("cuda"))
@@ -74,7 +102,11 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
     learner_rpc.set_timeout(30)
     learner_rpc.connect(addr)
 
-    time_batcher = moolib_amd.Batcher(unroll, device)
+    # overlapping sequences and actor-side priorities go through a SequenceBuilder
+    builder = None
+    if period is not None or actor_priorities:
+        builder = learner.sequence_builder(unroll, period)
+    time_batcher = moolib_amd.Batcher(unroll, device) if builder is None else None
     core_state = tuple(s.to(device) for s in learner.online.initial_state(batch_size=num_envs))
     start_state = core_state  # recurrent state at the start of the current unroll
     prev_action = torch.zeros(num_envs, dtype=torch.int64, device=device)
@@ -83,23 +115,44 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
     frames = sampled = learn_steps = 0
     add_futures = []
     metrics = None
+    priority_sum, priority_count = 0.0, 0  # of the actor's initial priorities
     while time.time() - t0 < seconds:
         # ---- act (epsilon-greedy on the dueling Q-values) ----
         obs = envs.step(0, prev_action).result()
         dev = {k: t.to(device, copy=True) for k, t in obs.items()}
         dev["prev_action"] = prev_action
         inputs = {k: dev[k].unsqueeze(0) for k in ("state", "reward", "done", "prev_action")}
-        action, core_state = learner.act(inputs, core_state, epsilon=epsilon)
-        action = action.squeeze(0)
-        frames += num_envs
-        time_batcher.stack(dict(
-            state=dev["state"], reward=dev["reward"], done=dev["done"],
-            prev_action=prev_action, action=action,
-        ))
+        if builder is None:
+            action, core_state = learner.act(inputs, core_state, epsilon=epsilon)
+            action = action.squeeze(0)
+            frames += num_envs
+            time_batcher.stack(dict(
+                state=dev["state"], reward=dev["reward"], done=dev["done"],
+                prev_action=prev_action, action=action,
+            ))
+        else:
+            before = core_state  # what the network held when it consumed this step
+            action, core_state, q = learner.act(
+                inputs, core_state, epsilon=epsilon, return_q=True
+            )
+            action = action.squeeze(0)
+            frames += num_envs
+            emitted = builder.append(
+                dict(state=dev["state"], reward=dev["reward"], done=dev["done"],
+                     prev_action=prev_action, action=action),
+                before, *(q if actor_priorities else (None, None)),
+            )
         prev_action = action
 
         # ---- feed replay: one item per environment sequence ----
-        if sumtree and not time_batcher.empty():
+        if builder is not None:
+            if emitted is not None:
+                items, priorities = emitted
+                if priorities is not None:
+                    priority_sum += priorities.sum()
+                    priority_count += num_envs
+                add_futures += _add_sequences(buf, actor_rpc, sumtree, items, priorities)
+        elif sumtree and not time_batcher.empty():
             # the whole [T, B, ...] unroll and its [1, B, H] start state, as they are
             items = dict(time_batcher.get())
             items = {k: items[k] for k in SEQUENCE_KEYS}
@@ -143,7 +196,7 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
     dt = time.time() - t0
     for f in add_futures:
         f.result()
-    return {
+    result = {
         "seconds": dt,
         "frames_acted": frames,
         "frames_per_s": frames / dt,
@@ -163,6 +216,13 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
         "fused_act": bool(fused_act),
         "device": str(device),
     }
+    if builder is not None:
+        result["period"] = builder.period
+        result["actor_priorities"] = bool(actor_priorities)
+        result["initial_priority_mean"] = (
+            float(priority_sum) / priority_count if priority_count else float("nan")
+        )
+    return result
 
 
 def main():
@@ -179,9 +239,14 @@ def main():
                     help="SumTreeReplayBuffer: batched adds, stratified time-major samples")
     ap.add_argument("--fused-act", action="store_true",
                     help="fused epsilon-greedy head, one epsilon_ladder epsilon per environment")
+    ap.add_argument("--period", type=int, default=None,
+                    help="start a sequence every N steps (overlapping sequences); default: unroll")
+    ap.add_argument("--actor-priorities", action="store_true",
+                    help="new sequences enter at the actor's own n-step TD priority")
     a = ap.parse_args()
     m = run(a.device, a.capacity, a.unroll, a.burn_in, a.batch_size, a.num_envs, a.seconds,
-            a.ipc, sumtree=a.sumtree, fused_act=a.fused_act)
+            a.ipc, sumtree=a.sumtree, fused_act=a.fused_act, period=a.period,
+            actor_priorities=a.actor_priorities)
     print(
         "r2d2: %.1fs, %d frames acted (%.0f/s), buffer %d/%d seqs, %d learner steps, "
         "%d sequences sampled (%.0f/s), mean |TD| %.4f, loss %.4f"
@@ -191,6 +256,9 @@ def main():
             m["mean_abs_td"], m["loss"],
         )
     )
+    if "initial_priority_mean" in m:
+        print("r2d2: period %d, mean initial priority %.4f"
+              % (m["period"], m["initial_priority_mean"]))
 
 
 if __name__ == "__main__":

@@ -18,6 +18,8 @@
 //   r2d2_loss_kernel (r2d2.hip.inc) — fused R2D2 loss: n-step double-Q
 //     targets under value rescaling, masked sequence loss, sequence
 //     priorities and d(loss)/d(q) in one launch, no atomics.
+//   actor_priority_kernel (r2d2.hip.inc) — the actor's initial sequence
+//     priorities from its own q_taken / q_max, one launch.
 //   act_categorical_kernel, act_eps_greedy_kernel (act.hip.inc) — the actor's
 //     action head: Philox4x32-10 sampling from a [seed, step] state on the
 //     device, one launch each.
@@ -1210,7 +1212,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("discounts"), py::arg("mask"), py::arg("is_weights"), py::arg("n"),
         py::arg("eps"), py::arg("rescale"), py::arg("eta"), py::arg("grad_scale"),
         py::arg("grad_out") = py::none());
-  m.attr("R2D2_MAX_T") = r2d2::kMaxT;  // longest sequence r2d2_loss accepts
+  m.def("r2d2_actor_priority", &r2d2_actor_priority,
+        "initial sequence priorities [K] and TD errors [T,K] from an actor's q_taken / q_max, "
+        "reward and done in the actor's layout; one launch (gfx950)",
+        py::arg("q_taken"), py::arg("q_max"), py::arg("reward"), py::arg("done"), py::arg("n"),
+        py::arg("discount"), py::arg("eps"), py::arg("rescale"), py::arg("eta"),
+        py::arg("burn_in"), py::arg("priority_out") = py::none(),
+        py::arg("td_out") = py::none());
+  m.attr("R2D2_MAX_T") = r2d2::kMaxT;  // longest sequence the r2d2 kernels accept
   m.def("replay_tree_update", &replay_tree_update,
         "sum-tree leaves <- priority^alpha (last wins), ancestors, max_priority (gfx950)",
         py::arg("tree"), py::arg("max_priority"), py::arg("slots"), py::arg("priorities"),

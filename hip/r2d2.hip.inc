@@ -195,7 +195,155 @@ __global__ __launch_bounds__(kThreads) void r2d2_loss_kernel(
   }
 }
 
+// Initial priority of an actor's sequence from its own Q-values: the loss
+// kernel without the argmax phase and without a gradient. Inputs are in the
+// actor's layout, reward[t] and done[t] arrive WITH step t, so the reward and
+// discount that follow action t are read from row t+1 here; the last row has
+// no successor and only bootstraps.
+//   - grid: one workgroup per environment k, 256 threads, thread t owns step t;
+//   - thread t stages boot_t = h^-1(q_max[t,k]), q_taken[t,k], r_t, g_t in LDS;
+//   - after a barrier it forms G_t and writes td[t,k] (zero for t = T-1 and
+//     for burn-in steps);
+//   - the block reduction of r2d2_loss_kernel writes priority[k].
+// Every output element is written exactly once, no atomics, no memset.
+__global__ __launch_bounds__(kThreads) void actor_priority_kernel(
+    const float* __restrict__ q_taken,  // [T,K]
+    const float* __restrict__ q_max,    // [T,K]
+    const float* __restrict__ reward,   // [T,K]
+    const uint8_t* __restrict__ done,   // [T,K], bool or uint8
+    float* __restrict__ td,             // [T,K]
+    float* __restrict__ priority,       // [K]
+    int T, int K, int n, int burn_in, float discount, float eps, int rescale, float eta,
+    float oneMinusEta) {
+#pragma clang fp contract(off)
+  __shared__ float sBoot[kMaxT];
+  __shared__ float sQa[kMaxT];
+  __shared__ float sReward[kMaxT];
+  __shared__ float sDiscount[kMaxT];
+  __shared__ double sSum[2][kWaves];
+  __shared__ float sMax[kWaves];
+
+  const int k = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid % kWave;
+  const int wave = tid / kWave;
+
+  if (tid < T) {
+    const int64_t i = (int64_t)tid * K + k;
+    const float boot = q_max[i];
+    sBoot[tid] = rescale ? inverseRescaleValue(boot, eps, 4.f * eps) : boot;
+    sQa[tid] = q_taken[i];
+    const bool more = tid < T - 1;  // row t+1 exists
+    sReward[tid] = more ? reward[i + K] : 0.f;
+    sDiscount[tid] = (more && done[i + K] == 0) ? discount : 0.f;
+  }
+  __syncthreads();
+
+  float delta = 0.f;
+  float valid = 0.f;
+  if (tid < T - 1) {
+    const int t = tid;
+    const int steps = min(n, T - 1 - t);
+    float G = 0.f;
+    float disc = 1.f;
+    for (int i = 0; i < steps; ++i) {
+      G = G + disc * sReward[t + i];
+      disc = disc * sDiscount[t + i];
+    }
+    G = G + disc * sBoot[t + steps];
+    if (rescale) G = rescaleValue(G, eps);
+    valid = t >= burn_in ? 1.f : 0.f;
+    delta = valid * (G - sQa[t]);
+  }
+  if (tid < T) td[(int64_t)tid * K + k] = delta;
+
+  const float absDelta = fabsf(delta);
+  double sumAbs = waveReduceSumF64((double)absDelta);
+  double sumValid = waveReduceSumF64((double)valid);
+  float maxAbs = waveReduceMax(absDelta);
+  if (lane == 0) {
+    sSum[0][wave] = sumAbs;
+    sSum[1][wave] = sumValid;
+    sMax[wave] = maxAbs;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < kWaves; ++w) {
+      sumAbs = sumAbs + sSum[0][w];
+      sumValid = sumValid + sSum[1][w];
+      maxAbs = fmaxf(maxAbs, sMax[w]);
+    }
+    float meanAbs = (float)sumAbs / fmaxf(1.f, (float)sumValid);
+    priority[k] = eta * maxAbs + oneMinusEta * meanAbs;
+  }
+}
+
 }  // namespace r2d2
+
+// priority [K], td [T,K] of an actor's sequences, in the actor's layout
+// (reward[t], done[t] arrive with step t). `priority_out` / `td_out`, if given,
+// are the buffers the results are written into (every element).
+std::vector<at::Tensor> r2d2_actor_priority(at::Tensor q_taken, at::Tensor q_max,
+                                            at::Tensor reward, at::Tensor done, int64_t n,
+                                            double discount, double eps, bool rescale,
+                                            double eta, int64_t burn_in,
+                                            c10::optional<at::Tensor> priority_out,
+                                            c10::optional<at::Tensor> td_out) {
+  TORCH_CHECK(q_taken.defined() && q_taken.is_cuda() && q_taken.scalar_type() == at::kFloat &&
+                  q_taken.dim() == 2 && q_taken.is_contiguous(),
+              "r2d2_actor_priority: q_taken must be a contiguous float32 CUDA tensor [T,K]");
+  const int64_t T = q_taken.size(0), K = q_taken.size(1);
+  TORCH_CHECK(T >= 1 && K >= 1, "r2d2_actor_priority: q_taken must be non-empty, got ",
+              q_taken.sizes());
+  TORCH_CHECK(T <= r2d2::kMaxT, "r2d2_actor_priority: T = ", T,
+              " exceeds the kernel's limit of ", r2d2::kMaxT, " steps per sequence");
+  TORCH_CHECK(K <= INT_MAX, "r2d2_actor_priority: K must fit in int32");
+  TORCH_CHECK(n >= 1, "r2d2_actor_priority: n_step must be >= 1, got ", n);
+  TORCH_CHECK(eps >= 0.0, "r2d2_actor_priority: eps must be >= 0, got ", eps);
+  TORCH_CHECK(eta >= 0.0 && eta <= 1.0, "r2d2_actor_priority: eta must be in [0,1], got ", eta);
+  TORCH_CHECK(burn_in >= 0, "r2d2_actor_priority: burn_in must be >= 0, got ", burn_in);
+  auto check = [&](const at::Tensor& t, bool flag, at::IntArrayRef shape, const char* name) {
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.device() == q_taken.device(),
+                "r2d2_actor_priority: ", name, " must be on the same CUDA device as q_taken");
+    if (flag) {
+      TORCH_CHECK(t.scalar_type() == at::kBool || t.scalar_type() == at::kByte,
+                  "r2d2_actor_priority: ", name, " must be bool or uint8, got ", t.scalar_type());
+    } else {
+      TORCH_CHECK(t.scalar_type() == at::kFloat, "r2d2_actor_priority: ", name,
+                  " must be Float, got ", t.scalar_type());
+    }
+    TORCH_CHECK(t.sizes() == shape, "r2d2_actor_priority: ", name, " must have shape ", shape,
+                ", got ", t.sizes());
+    TORCH_CHECK(t.is_contiguous(), "r2d2_actor_priority: ", name, " must be contiguous");
+  };
+  check(q_max, false, {T, K}, "q_max");
+  check(reward, false, {T, K}, "reward");
+  check(done, true, {T, K}, "done");
+  at::Tensor priority, td;
+  if (priority_out.has_value() && priority_out->defined()) {
+    check(*priority_out, false, {K}, "priority_out");
+    priority = *priority_out;
+  } else {
+    priority = at::empty({K}, q_taken.options());
+  }
+  if (td_out.has_value() && td_out->defined()) {
+    check(*td_out, false, {T, K}, "td_out");
+    td = *td_out;
+  } else {
+    td = at::empty({T, K}, q_taken.options());
+  }
+  // windows end at T-1 and no step past it is valid anyway
+  const int nSteps = (int)std::min<int64_t>(n, r2d2::kMaxT);
+  const int burnIn = (int)std::min<int64_t>(burn_in, r2d2::kMaxT);
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  hipLaunchKernelGGL(r2d2::actor_priority_kernel, dim3((unsigned)K), dim3(r2d2::kThreads), 0,
+                     stream, q_taken.data_ptr<float>(), q_max.data_ptr<float>(),
+                     reward.data_ptr<float>(), static_cast<const uint8_t*>(done.data_ptr()),
+                     td.data_ptr<float>(), priority.data_ptr<float>(), (int)T, (int)K, nSteps,
+                     burnIn, (float)discount, (float)eps, rescale ? 1 : 0, (float)eta,
+                     (float)(1.0 - eta));
+  return {priority, td};
+}
 
 // td [T,B], loss_seq [B], priority [B], grad_q [T,B,A]. `grad_out`, if given,
 // is the [T,B,A] buffer the gradient is written into (every element).

@@ -24,6 +24,11 @@ autograd sees a single Function whose backward scales the precomputed
 gradient. The plain-torch path below is the CPU implementation and the fp32
 numerics reference of the kernel tests: it performs the same operations in
 the same order.
+
+`actor_priorities` is the actor's side of the same quantity: the initial
+priority of a freshly acted sequence from the Q-values the act head returned
+(q_taken, q_max), with reward and done in the actor's layout. One launch of
+moolib_amd._kernels.r2d2_actor_priority on the GPU.
 """
 import collections
 import os
@@ -79,9 +84,15 @@ def _kernels():
 @torch.no_grad()
 def _rescaled_returns(q, q_target, rewards, discounts, n_step, eps, rescale):
     """h(G_t) for t < T-1: [T-1, B]. No gradient flows into the target."""
-    T = q.shape[0]
     a_star = q.argmax(dim=-1, keepdim=True)  # first maximal index
     boot = q_target.gather(-1, a_star).squeeze(-1)
+    return _returns_from_bootstrap(boot, rewards, discounts, n_step, eps, rescale)
+
+
+@torch.no_grad()
+def _returns_from_bootstrap(boot, rewards, discounts, n_step, eps, rescale):
+    """h(G_t) for t < T-1 from the value [T, B] each step bootstraps with."""
+    T = boot.shape[0]
     if rescale:
         boot = inverse_value_rescale(boot, eps)
     Tm = T - 1
@@ -92,7 +103,7 @@ def _rescaled_returns(q, q_target, rewards, discounts, n_step, eps, rescale):
         m = Tm - i
         G[:m] += disc[:m] * rewards[i:Tm]
         disc[:m] *= discounts[i:Tm]
-    boot_index = (torch.arange(Tm, device=q.device) + n_step).clamp(max=T - 1)
+    boot_index = (torch.arange(Tm, device=boot.device) + n_step).clamp(max=T - 1)
     G += disc * boot[boot_index]
     if rescale:
         G = value_rescale(G, eps)
@@ -165,3 +176,89 @@ def r2d2_loss(q, q_target, actions, rewards, discounts, mask, is_weights,
     if q.is_cuda and _kernels() is not None:
         return R2D2LossReturns(*_FusedR2D2Loss.apply(*args, n_step, eps, rescale, eta))
     return _eager(*args, n_step, eps, rescale, eta)
+
+
+ActorPriorityReturns = collections.namedtuple("ActorPriorityReturns", ["priorities", "td_errors"])
+
+
+@torch.no_grad()
+def _eager_actor_priorities(q_taken, q_max, reward, done, n_step, discount, eps, rescale, eta,
+                            burn_in):
+    T = q_taken.shape[0]
+    # r_t and gamma_t FOLLOW a_t: they arrive with step t+1. The last step has
+    # no successor; it only bootstraps.
+    last = torch.zeros_like(reward[:1])
+    rewards = torch.cat([reward[1:], last], dim=0)
+    gamma = torch.full_like(reward[1:], discount)
+    discounts = torch.cat([torch.where(done[1:] != 0, torch.zeros_like(gamma), gamma), last], dim=0)
+    G = _returns_from_bootstrap(q_max, rewards, discounts, n_step, eps, rescale)
+    valid = torch.zeros_like(reward)
+    valid[burn_in:T - 1] = 1.0
+    td = torch.cat([valid[:-1] * (G - q_taken[:-1]), last], dim=0)
+    abs_td = td.abs()
+    mean_abs = abs_td.sum(dim=0) / valid.sum(dim=0).clamp(min=1.0)
+    priorities = eta * abs_td.max(dim=0).values + (1.0 - eta) * mean_abs
+    return ActorPriorityReturns(priorities, td)
+
+
+def actor_priorities(q_taken, q_max, reward, done, *, n_step=5, discount=0.997, eps=1e-3,
+                     rescale=True, eta=0.9, burn_in=0, out=None):
+    """Initial replay priorities of an actor's sequences, from its own Q-values.
+
+    q_taken / q_max [T,K] are the Q-values of the actions taken and of the
+    greedy ones (R2D2Learner.act(..., return_q=True)); reward [T,K] and done
+    [T,K] (bool or uint8) are in the actor's layout, as replay items hold them:
+    reward[t] and done[t] arrive WITH step t, so they follow action t-1. The
+    shift by one step happens in here:
+
+        r_t = reward[t+1],  g_t = done[t+1] ? 0 : discount        (t < T-1)
+        boot_s  = h^-1(q_max[s])
+        G_t     = n-step return of r, g, boot as in r2d2_loss
+        delta_t = valid_t (h(G_t) - q_taken[t]),  valid_t = 1 for burn_in <= t < T-1
+        priority[k] = eta max_t|delta_t| + (1-eta) sum_t|delta_t| / max(1, sum_t valid_t)
+
+    which is what r2d2_loss returns when the target network equals the online
+    one. Rewards are not clipped. Returns ActorPriorityReturns(priorities [K],
+    td_errors [T,K]). `out`, a (priorities, td_errors) pair of contiguous fp32
+    buffers, receives the results. One launch of the fused gfx950 kernel on the
+    GPU (T up to KERNEL_MAX_T, no host synchronisation), plain torch on the
+    CPU or with MOOLIB_AMD_NO_R2D2_KERNEL set.
+    """
+    n_step, discount, eps = int(n_step), float(discount), float(eps)
+    rescale, eta, burn_in = bool(rescale), float(eta), int(burn_in)
+    if n_step < 1:
+        raise ValueError("actor_priorities: n_step must be >= 1, got %d" % n_step)
+    if eps < 0:
+        raise ValueError("actor_priorities: eps must be >= 0, got %r" % eps)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError("actor_priorities: eta must be in [0,1], got %r" % eta)
+    if burn_in < 0:
+        raise ValueError("actor_priorities: burn_in must be >= 0, got %d" % burn_in)
+    if q_taken.dim() != 2 or q_taken.shape[0] < 1:
+        raise ValueError("actor_priorities: q_taken must be [T,K] with T >= 1, got %s"
+                         % (tuple(q_taken.shape),))
+    for name, t in (("q_max", q_max), ("reward", reward), ("done", done)):
+        if t.shape != q_taken.shape:
+            raise ValueError("actor_priorities: %s has shape %s, q_taken %s"
+                             % (name, tuple(t.shape), tuple(q_taken.shape)))
+        if t.device != q_taken.device:
+            raise ValueError("actor_priorities: %s is on %s, q_taken on %s"
+                             % (name, t.device, q_taken.device))
+    if done.dtype not in (torch.bool, torch.uint8):
+        done = done != 0
+    args = (
+        q_taken.detach().float().contiguous(),
+        q_max.detach().float().contiguous(),
+        reward.detach().float().contiguous(),
+        done.contiguous(),
+    )
+    if q_taken.is_cuda and _kernels() is not None:
+        priority_out, td_out = out if out is not None else (None, None)
+        return ActorPriorityReturns(*_kernels().r2d2_actor_priority(
+            *args, n_step, discount, eps, rescale, eta, burn_in, priority_out, td_out))
+    result = _eager_actor_priorities(*args, n_step, discount, eps, rescale, eta, burn_in)
+    if out is not None:
+        out[0].copy_(result.priorities)
+        out[1].copy_(result.td_errors)
+        return ActorPriorityReturns(out[0], out[1])
+    return result

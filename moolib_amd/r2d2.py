@@ -7,8 +7,10 @@ Works with any model that follows AtariNet's forward contract
 network acts as a dueling Q-network, `baseline` is V and `policy_logits` is
 the advantage stream (ops.r2d2.dueling_q). The loss, its gradient and the
 sequence priorities come from ops.r2d2.r2d2_loss — one fused HIP kernel on an
-MI355X.
+MI355X. On the actor's side, SequenceBuilder cuts the stream of steps into
+overlapping sequences and gives each its initial priority.
 """
+import collections
 import contextlib
 import copy
 import dataclasses
@@ -16,7 +18,7 @@ import dataclasses
 import torch
 
 from moolib_amd.ops import act as act_ops
-from moolib_amd.ops.r2d2 import dueling_q, r2d2_loss
+from moolib_amd.ops.r2d2 import actor_priorities, dueling_q, r2d2_loss
 
 
 @dataclasses.dataclass
@@ -33,6 +35,125 @@ class R2D2Config:
     fused_optimizer: bool = False  # clip + Adam as one fused flat step (optim.FlatAdam)
     fused_act: bool = False  # act() head as one fused launch (ops.act.epsilon_greedy_dueling)
     seed: int = None  # of the fused act head's sampler state; None takes a fresh one
+
+
+class SequenceBuilder:
+    """Cuts an actor's stream of steps into replay sequences of `unroll` steps
+    that start every `period` steps (R2D2: unroll 80, period 40), each with
+    the recurrent state at its own start and, given the act head's Q-values,
+    its initial priority (ops.r2d2.actor_priorities).
+
+        b = SequenceBuilder(unroll, period)            # period None: disjoint
+        out = b.append(step, core_state, q_taken, q_max)
+
+    `step` is a dict of [K, ...] tensors with at least `reward` and `done`;
+    `core_state` is the (h, c) tuple [1, K, H] the network held BEFORE it
+    consumed this step, or () for a model without a core; `q_taken` / `q_max`
+    are [K] or [1, K]. `append` returns None until a window is complete, then
+    (items, priorities): every leaf stacked [unroll, K, ...], `core_h` /
+    `core_c` of the window's first step if there is a core, and priorities
+    [K] (None if no Q-values are given). Sequence j covers the global steps
+    [j * period, j * period + unroll).
+
+    Emitted tensors are the builder's window buffers, handed over: the next
+    window starts in fresh ones that receive the last `unroll - period` rows,
+    so nothing emitted is written again and source and destination of the tail
+    copy never overlap. The recurrent state is cloned at every step whose
+    index is a multiple of `period` (the caller's tensors may be the static
+    outputs of a captured graph). Nothing is read back to the host.
+    """
+
+    _Q_KEYS = ("q_taken", "q_max")
+
+    def __init__(self, unroll, period=None, n_step=5, discount=0.997, eps=1e-3, eta=0.9,
+                 burn_in=0):
+        self.unroll = int(unroll)
+        self.period = self.unroll if period is None else int(period)
+        if self.unroll < 1:
+            raise ValueError("SequenceBuilder: unroll must be >= 1, got %d" % self.unroll)
+        if not 1 <= self.period <= self.unroll:
+            raise ValueError("SequenceBuilder: period must be in [1, unroll = %d], got %d"
+                             % (self.unroll, self.period))
+        self.priority_args = dict(n_step=n_step, discount=discount, eps=eps, eta=eta,
+                                  burn_in=burn_in)
+        self.num_envs = None
+        self.with_q = None
+        self.window = None  # leaf name -> [unroll, K, ...]; the Q rows under _Q_KEYS
+        self.q_window = None
+        self.fill = 0  # rows of the window that are written
+        self.step_index = 0  # global index of the next step
+        self.starts = collections.deque()  # core states of the sequences not yet emitted
+
+    def _check(self, step, core_state, q):
+        for key in ("reward", "done"):
+            if key not in step:
+                raise ValueError("SequenceBuilder.append: step has no %r" % key)
+        for key in ("core_h", "core_c"):
+            if key in step:
+                raise ValueError("SequenceBuilder.append: %r is the builder's own key" % key)
+        K = step["reward"].shape[0]
+        if self.num_envs is None:
+            self.num_envs, self.with_q = K, q is not None
+        if len(core_state) not in (0, 2):
+            raise ValueError("SequenceBuilder.append: core_state must be (h, c) or ()")
+        for name, t in list(step.items()) + [("q", t) for t in (q or ())]:
+            if t.dim() < 1 or t.shape[0] != self.num_envs:
+                raise ValueError("SequenceBuilder.append: %s has shape %s, expected %d environments"
+                                 % (name, tuple(t.shape), self.num_envs))
+        for s in core_state:
+            if s.dim() != 3 or s.shape[1] != self.num_envs:
+                raise ValueError("SequenceBuilder.append: core state of shape %s, expected "
+                                 "[1, %d, H]" % (tuple(s.shape), self.num_envs))
+        if (q is not None) != self.with_q:
+            raise ValueError("SequenceBuilder.append: Q-values must come with every step or none")
+        if self.window is not None and set(step) != set(self.window):
+            raise ValueError("SequenceBuilder.append: step keys %s, expected %s"
+                             % (sorted(step), sorted(self.window)))
+
+    def _fresh(self, rows):
+        return {k: t.new_empty((self.unroll,) + tuple(t.shape)) for k, t in rows.items()}
+
+    @torch.no_grad()
+    def append(self, step, core_state=(), q_taken=None, q_max=None):
+        if (q_taken is None) != (q_max is None):
+            raise ValueError("SequenceBuilder.append: q_taken and q_max come together")
+        q = None
+        if q_taken is not None:
+            q = tuple(t.reshape(-1) if t.dim() == 2 and t.shape[0] == 1 else t
+                      for t in (q_taken, q_max))
+        self._check(step, core_state, q)
+        q_rows = dict(zip(self._Q_KEYS, q)) if q is not None else {}
+        if self.window is None:
+            self.window, self.q_window = self._fresh(step), self._fresh(q_rows)
+        if self.step_index % self.period == 0:
+            self.starts.append(tuple(s.clone() for s in core_state))
+        for window, rows in ((self.window, step), (self.q_window, q_rows)):
+            for k, t in rows.items():
+                window[k][self.fill].copy_(t, non_blocking=True)
+        self.fill += 1
+        self.step_index += 1
+        if self.fill < self.unroll:
+            return None
+
+        items, q_items = self.window, self.q_window
+        keep = self.unroll - self.period
+        self.window, self.q_window = self._fresh(step), self._fresh(q_rows)
+        for new, old in ((self.window, items), (self.q_window, q_items)):
+            for k in new:
+                new[k][:keep].copy_(old[k][self.period:])
+        self.fill = keep
+        priorities = None
+        if self.with_q:
+            device = q_items["q_taken"].device
+            priorities = actor_priorities(
+                q_items["q_taken"], q_items["q_max"], items["reward"].to(device),
+                items["done"].to(device), **self.priority_args
+            ).priorities
+        start = self.starts.popleft()
+        items = dict(items)
+        if start:
+            items["core_h"], items["core_c"] = start
+        return items, priorities
 
 
 class R2D2Learner:
@@ -113,6 +234,14 @@ class R2D2Learner:
             taken = q.gather(-1, action.unsqueeze(-1)).squeeze(-1)
             return action, core_state, (taken, q.gather(-1, greedy.unsqueeze(-1)).squeeze(-1))
         return action, core_state
+
+    def sequence_builder(self, unroll, period=None):
+        """A SequenceBuilder whose priorities use this learner's n_step,
+        discount, eps, eta and burn_in, i.e. the ones `learn` will return for
+        the same sequence while the target network equals the online one."""
+        cfg = self.config
+        return SequenceBuilder(unroll, period, n_step=cfg.n_step, discount=cfg.discount,
+                               eps=cfg.eps, eta=cfg.eta, burn_in=cfg.burn_in)
 
     def sync_target(self):
         self.target.load_state_dict(self.online.state_dict())
