@@ -407,6 +407,7 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 #include "conv3x3.hip.inc"
 #include "wgrad3x3.hip.inc"
 #include "lstm.hip.inc"
+#include "lstm_wide.hip.inc"
 #include "r2d2.hip.inc"
 
 // ------------------------------------------------------------ wrappers
@@ -493,6 +494,119 @@ std::vector<at::Tensor> lstm_fused_bwd(at::Tensor gates, at::Tensor cs, at::Tens
                      reinterpret_cast<const lstm::bf16*>(whhPackedN.data_ptr()),
                      reinterpret_cast<lstm::bf16*>(dG.data_ptr()),
                      reinterpret_cast<lstm::bf16*>(dh0.data_ptr()), dc0.data_ptr<float>(), T, B);
+  return {dG, dh0, dc0};
+}
+
+// ---- hidden sizes 128 and 512: the register-resident scan (lstm_wide.hip.inc)
+
+template <int H, bool SAVE>
+static std::vector<at::Tensor> lstmWideFwdLaunch(const at::Tensor& X, const at::Tensor& notdone,
+                                                 const at::Tensor& h0, const at::Tensor& c0,
+                                                 const at::Tensor& whhPacked) {
+  using bf16 = lstm::bf16;
+  int T = X.size(0), B = X.size(1);
+  auto opts = X.options();
+  auto fopts = opts.dtype(at::kFloat);
+  auto Hs = at::empty({T, B, H}, opts);
+  auto hT = at::empty({B, H}, opts);
+  auto cT = at::empty({B, H}, fopts);
+  std::vector<at::Tensor> out;
+  lstm_wide::SavedOut<SAVE> saved;
+  if constexpr (SAVE) {
+    auto gates = at::empty({T, B, 4 * H}, opts);
+    auto cs = at::empty({T, B, H}, fopts);
+    saved.gates = reinterpret_cast<bf16*>(gates.data_ptr());
+    saved.c = cs.data_ptr<float>();
+    out = {Hs, gates, cs, hT, cT};
+  } else {
+    out = {Hs, hT, cT};
+  }
+  int blocks = (B + lstm_wide::Geo<H>::kBM - 1) / lstm_wide::Geo<H>::kBM;
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  hipLaunchKernelGGL((lstm_wide::lstm_wide_fwd_kernel<H, SAVE>), dim3(blocks),
+                     dim3(lstm_wide::Geo<H>::kWaves * 64), 0, stream,
+                     reinterpret_cast<const bf16*>(X.data_ptr()), notdone.data_ptr<float>(),
+                     reinterpret_cast<const bf16*>(h0.data_ptr()), c0.data_ptr<float>(),
+                     reinterpret_cast<const bf16*>(whhPacked.data_ptr()),
+                     reinterpret_cast<bf16*>(Hs.data_ptr()), saved,
+                     reinterpret_cast<bf16*>(hT.data_ptr()), cT.data_ptr<float>(), T, B);
+  return out;
+}
+
+// save=true returns (H, gates, cs, hT, cT) as lstm_fused_fwd does; save=false
+// runs the forward-only variant and returns (H, hT, cT), allocating nothing else.
+std::vector<at::Tensor> lstm_wide_fwd(at::Tensor X, at::Tensor notdone, at::Tensor h0,
+                                      at::Tensor c0, at::Tensor whhPacked, bool save) {
+  TORCH_CHECK(X.is_cuda() && X.dtype() == at::kBFloat16 && X.dim() == 3,
+              "lstm wide fwd: X [T,B,4H] bf16");
+  TORCH_CHECK(X.is_contiguous(), "lstm wide fwd: X must be contiguous");
+  int64_t T = X.size(0), B = X.size(1), H = X.size(2) / 4;
+  TORCH_CHECK(X.size(2) == 4 * H && (H == 128 || H == 512),
+              "lstm wide fwd: hidden size must be 128 or 512 (256 runs on lstm_fused_fwd), got X [",
+              X.sizes(), "]");
+  TORCH_CHECK(T > 0 && B > 0, "lstm wide fwd: empty sequence or batch");
+  checkLstmArg(notdone, X, at::kFloat, {T, B}, "lstm wide fwd", "notdone");
+  checkLstmArg(h0, X, at::kBFloat16, {B, H}, "lstm wide fwd", "h0");
+  checkLstmArg(c0, X, at::kFloat, {B, H}, "lstm wide fwd", "c0");
+  checkLstmArg(whhPacked, X, at::kBFloat16, {4 * H * H}, "lstm wide fwd", "whhPacked");
+  if (H == 128)
+    return save ? lstmWideFwdLaunch<128, true>(X, notdone, h0, c0, whhPacked)
+                : lstmWideFwdLaunch<128, false>(X, notdone, h0, c0, whhPacked);
+  return save ? lstmWideFwdLaunch<512, true>(X, notdone, h0, c0, whhPacked)
+              : lstmWideFwdLaunch<512, false>(X, notdone, h0, c0, whhPacked);
+}
+
+template <int H>
+static void lstmWideBwdLaunch(const at::Tensor& gates, const at::Tensor& cs, const at::Tensor& c0,
+                              const at::Tensor& notdone, const at::Tensor& dH,
+                              const at::Tensor& dhT, const at::Tensor& dcT,
+                              const at::Tensor& whhPackedN, at::Tensor& dG, at::Tensor& dh0,
+                              at::Tensor& dc0) {
+  using bf16 = lstm::bf16;
+  int T = gates.size(0), B = gates.size(1);
+  int blocks = (B + lstm_wide::Geo<H>::kBM - 1) / lstm_wide::Geo<H>::kBM;
+  hipStream_t stream = c10::hip::getCurrentHIPStream().stream();
+  hipLaunchKernelGGL(lstm_wide::lstm_wide_bwd_kernel<H>, dim3(blocks),
+                     dim3(lstm_wide::Geo<H>::kWaves * 64), 0, stream,
+                     reinterpret_cast<const bf16*>(gates.data_ptr()), cs.data_ptr<float>(),
+                     c0.data_ptr<float>(), notdone.data_ptr<float>(),
+                     reinterpret_cast<const bf16*>(dH.data_ptr()),
+                     dhT.numel() > 0 ? reinterpret_cast<const bf16*>(dhT.data_ptr()) : nullptr,
+                     dcT.numel() > 0 ? dcT.data_ptr<float>() : nullptr,
+                     reinterpret_cast<const bf16*>(whhPackedN.data_ptr()),
+                     reinterpret_cast<bf16*>(dG.data_ptr()),
+                     reinterpret_cast<bf16*>(dh0.data_ptr()), dc0.data_ptr<float>(), T, B);
+}
+
+std::vector<at::Tensor> lstm_wide_bwd(at::Tensor gates, at::Tensor cs, at::Tensor c0,
+                                      at::Tensor notdone, at::Tensor dH, at::Tensor dhT,
+                                      at::Tensor dcT, at::Tensor whhPackedN) {
+  TORCH_CHECK(gates.is_cuda() && gates.dtype() == at::kBFloat16 && gates.dim() == 3 &&
+                  gates.is_contiguous(),
+              "lstm wide bwd: gates [T,B,4H] contiguous bf16");
+  int64_t T = gates.size(0), B = gates.size(1), H = gates.size(2) / 4;
+  TORCH_CHECK(gates.size(2) == 4 * H && (H == 128 || H == 512),
+              "lstm wide bwd: hidden size must be 128 or 512 (256 runs on lstm_fused_bwd), got "
+              "gates [", gates.sizes(), "]");
+  TORCH_CHECK(T > 0 && B > 0, "lstm wide bwd: empty sequence or batch");
+  checkLstmArg(cs, gates, at::kFloat, {T, B, H}, "lstm wide bwd", "cs");
+  checkLstmArg(c0, gates, at::kFloat, {B, H}, "lstm wide bwd", "c0");
+  checkLstmArg(notdone, gates, at::kFloat, {T, B}, "lstm wide bwd", "notdone");
+  checkLstmArg(dH, gates, at::kBFloat16, {T, B, H}, "lstm wide bwd", "dH");
+  // dhT / dcT: an undefined or EMPTY tensor means "no gradient", as in lstm_fused_bwd
+  if (!dhT.defined()) dhT = at::empty({0}, gates.options());
+  if (!dcT.defined()) dcT = at::empty({0}, gates.options().dtype(at::kFloat));
+  if (dhT.numel() > 0) checkLstmArg(dhT, gates, at::kBFloat16, {B, H}, "lstm wide bwd", "dhT");
+  if (dcT.numel() > 0) checkLstmArg(dcT, gates, at::kFloat, {B, H}, "lstm wide bwd", "dcT");
+  checkLstmArg(whhPackedN, gates, at::kBFloat16, {4 * H * H}, "lstm wide bwd", "whhPackedN");
+  auto opts = gates.options();
+  auto dG = at::empty({T, B, 4 * H}, opts);
+  auto dh0 = at::empty({B, H}, opts);
+  auto dc0 = at::empty({B, H}, opts.dtype(at::kFloat));
+  if (H == 128)
+    lstmWideBwdLaunch<128>(gates, cs, c0, notdone, dH, dhT, dcT, whhPackedN, dG, dh0, dc0);
+  else
+    lstmWideBwdLaunch<512>(gates, cs, c0, notdone, dH, dhT, dcT, whhPackedN, dG, dh0, dc0);
   return {dG, dh0, dc0};
 }
 
@@ -1204,6 +1318,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "3x3/s1/p1 conv weight gradient on MFMA (row-slab LDS staging, gfx950)");
   m.def("lstm_fused_fwd", &lstm_fused_fwd, "fused masked LSTM sequence scan fwd (MFMA, gfx950)");
   m.def("lstm_fused_bwd", &lstm_fused_bwd, "fused masked LSTM sequence scan bwd (MFMA, gfx950)");
+  m.def("lstm_wide_fwd", &lstm_wide_fwd,
+        "register-resident masked LSTM scan fwd, hidden 128/512; save=False is forward-only");
+  m.def("lstm_wide_bwd", &lstm_wide_bwd, "register-resident masked LSTM scan bwd, hidden 128/512");
   m.def("vtrace_from_log_rhos", &vtrace_from_log_rhos, "fused V-trace scan (gfx950)");
   m.def("impala_loss", &impala_loss, "fused IMPALA loss fwd+grad (gfx950)");
   m.def("r2d2_loss", &r2d2_loss,

@@ -4,8 +4,10 @@ Architecture parity with the reference model (examples/atari/models.py:9-153)
 — this exact config is what BASELINE.json's headline benchmark names:
 3 blocks of (3x3 conv -> 3x3/2 maxpool -> 2 residual blocks) with 16/32/32
 channels, FC 3872->256, one-hot prev action + clipped reward appended,
-optional LSTM(256), policy + baseline heads, multinomial sampling inside
-forward.
+optional LSTM (256 units by default; `lstm_size` sets another width, e.g.
+R2D2's 512), policy + baseline heads, multinomial sampling inside forward.
+On CUDA in bf16 the LSTM runs as one fused scan for 128, 256 and 512 units
+(ops/lstm.py); any other width takes the per-step loop over nn.LSTM.
 
 MI355X notes: compute is bf16 (autocast over fp32 master weights, or bf16
 shadow weights); the actor path is hipGraph-captured by the learner loop
@@ -121,7 +123,7 @@ class ConvSection(nn.Module):
 
 
 class AtariNet(nn.Module):
-    def __init__(self, num_actions=18, input_channels=4, use_lstm=False):
+    def __init__(self, num_actions=18, input_channels=4, use_lstm=False, lstm_size=256):
         super().__init__()
         self.num_actions = num_actions
         self.use_lstm = use_lstm
@@ -137,8 +139,8 @@ class AtariNet(nn.Module):
         self.fc = nn.Linear(3872, 256)
         core_in = self.fc.out_features + num_actions + 1
         if use_lstm:
-            self.core = nn.LSTM(core_in, 256, num_layers=1)
-            core_in = 256
+            self.core = nn.LSTM(core_in, lstm_size, num_layers=1)
+            core_in = lstm_size
         self.policy = nn.Linear(core_in, num_actions)
         self.baseline = nn.Linear(core_in, 1)
         # Optional dedicated RNG for the in-forward multinomial: hipGraph
@@ -268,7 +270,7 @@ class AtariNet(nn.Module):
         return out, core_state
 
 
-def create_model(num_actions=18, use_lstm=False, device="cpu"):
-    model = AtariNet(num_actions=num_actions, use_lstm=use_lstm)
+def create_model(num_actions=18, use_lstm=False, device="cpu", lstm_size=256):
+    model = AtariNet(num_actions=num_actions, use_lstm=use_lstm, lstm_size=lstm_size)
     model.to(device)
     return model

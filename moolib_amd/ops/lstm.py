@@ -4,11 +4,25 @@ Replaces the T-step Python loop over nn.LSTM in the IMPALA model with one
 kernel launch per direction (see hip/lstm.hip.inc). The input projection
 x @ W_ih^T + b runs as one hipBLASLt GEMM over all T steps; the recurrent
 part (h @ W_hh^T on mfma_f32_16x16x32_bf16, gates, done-masking) runs in
-LDS-resident state. Hidden size fixed at 256 (the IMPALA config).
+one launch per direction, on one of two kernel families:
+
+* hidden size 256 (the IMPALA config): hip/lstm.hip.inc, with h, c and the
+  pre-activation gates resident in LDS. Always saves gates and cell states.
+* hidden sizes 128 and 512 (512 is R2D2's core): hip/lstm_wide.hip.inc, with
+  c, the gates and the running gradients in registers and only the MFMA A
+  operand in LDS. When grad mode is off, or no input requires a gradient, its
+  forward-only variant runs: the same instruction sequence without the
+  [T,B,4H] gate and [T,B,H] cell-state stores, bit-identical H, hT and cT.
+
+Any other hidden size is not served here (`available` is False).
+notdone is 0 or 1; the kernels do not check it.
 """
 import os
 
 import torch
+
+
+WIDE_SIZES = (128, 512)  # served by hip/lstm_wide.hip.inc; 256 by hip/lstm.hip.inc
 
 
 def _kernels():
@@ -22,7 +36,7 @@ def _kernels():
 
 def available(hidden_size, device):
     return (
-        hidden_size == 256
+        hidden_size in (256,) + WIDE_SIZES
         and device.type == "cuda"
         and _kernels() is not None
         and not os.environ.get("MOOLIB_AMD_NO_LSTM_KERNEL")
@@ -76,7 +90,61 @@ class _FusedLSTMScan(torch.autograd.Function):
     # c0 f32 <- dc0 f32; w_hh gets fp32 (autograd casts to the param dtype).
 
 
+class _WideLSTMScan(torch.autograd.Function):
+    """The same contract as _FusedLSTMScan over the 128/512 kernels."""
+
+    @staticmethod
+    def forward(ctx, X, notdone, h0, c0, w_hh):
+        k = _kernels()
+        w = w_hh.detach().to(torch.bfloat16)
+        packed_t = pack_mfma_b(w.t().contiguous())  # [H, 4H]
+        notdone, h0, c0 = notdone.contiguous(), h0.contiguous(), c0.contiguous()
+        H, gates, cs, hT, cT = k.lstm_wide_fwd(X.contiguous(), notdone, h0, c0, packed_t, True)
+        ctx.save_for_backward(gates, cs, c0, notdone, w, h0, H)
+        return H, hT, cT
+
+    @staticmethod
+    def backward(ctx, dH, dhT, dcT):
+        k = _kernels()
+        gates, cs, c0, notdone, w, h0, H = ctx.saved_tensors
+        packed_n = pack_mfma_b(w.contiguous())  # [4H, H]
+        empty = torch.Tensor()
+        dG, dh0, dc0 = k.lstm_wide_bwd(
+            gates,
+            cs,
+            c0,
+            notdone,
+            dH.contiguous().to(torch.bfloat16),
+            dhT.contiguous().to(torch.bfloat16) if dhT is not None else empty,
+            dcT.contiguous().float() if dcT is not None else empty,
+            packed_n,
+        )
+        T, B, _ = dG.shape
+        # dW_hh = dG^T @ h_masked_prev, as in _FusedLSTMScan.backward
+        Hm = torch.cat([h0.unsqueeze(0), H[:-1]]) * notdone.unsqueeze(-1).to(H.dtype)
+        dW = dG.reshape(T * B, -1).t().float() @ Hm.reshape(T * B, -1).float()
+        return dG, None, dh0, dc0, dW
+
+
 def fused_lstm_scan(X, notdone, h0, c0, w_hh):
-    """X [T,B,1024] bf16; notdone [T,B] f32; h0 [B,256] bf16; c0 [B,256] f32.
-    Returns (H [T,B,256] bf16, hT [B,256] bf16, cT [B,256] f32)."""
-    return _FusedLSTMScan.apply(X, notdone, h0, c0, w_hh)
+    """X [T,B,4H] bf16; notdone [T,B] f32, 0 or 1; h0 [B,H] bf16; c0 [B,H] f32;
+    w_hh [4H,H], with H in (128, 256, 512).
+    Returns (H [T,B,H] bf16, hT [B,H] bf16, cT [B,H] f32).
+
+    H == 256 runs the LDS-resident kernels. 128 and 512 run the register-
+    resident ones, forward-only (nothing saved, plain tensors returned) when
+    grad mode is off or no input requires a gradient."""
+    hidden = w_hh.shape[1]
+    if hidden == 256:
+        return _FusedLSTMScan.apply(X, notdone, h0, c0, w_hh)
+    if hidden not in WIDE_SIZES:
+        raise ValueError(
+            "fused_lstm_scan: hidden size %d has no kernel (128, 256 and 512 do)" % hidden
+        )
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (X, h0, c0, w_hh)):
+        return _WideLSTMScan.apply(X, notdone, h0, c0, w_hh)
+    packed_t = pack_mfma_b(w_hh.detach().to(torch.bfloat16).t().contiguous())
+    H, hT, cT = _kernels().lstm_wide_fwd(
+        X.contiguous(), notdone.contiguous(), h0.contiguous(), c0.contiguous(), packed_t, False
+    )
+    return H, hT, cT
