@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "message.h"
+#include "stager.h"
 
 namespace mrl {
 
@@ -98,6 +99,7 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
     if (numWorkers_ > batchSize_) numWorkers_ = batchSize_;
 
     computeLayout();
+    inFlight_.reset(new std::atomic<bool>[numBatches_]());
     if (segBytes < static_cast<int64_t>(dataOff_) + (64 << 20)) segBytes = dataOff_ + (512 << 20);
     segBytes_ = segBytes;
 
@@ -181,6 +183,7 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
     segBytes_ = ph->segBytes;
     munmap(peek, sizeof(Header));
     computeLayout();
+    inFlight_.reset(new std::atomic<bool>[numBatches_]());
     base_ = static_cast<char*>(
         mmap(nullptr, segBytes_, PROT_READ | PROT_WRITE, MAP_SHARED, shmFd_, 0));
     if (base_ == MAP_FAILED) throw RpcError("envrunner: mmap failed");
@@ -200,6 +203,9 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
   }
 
   ~EnvPoolImpl() {
+    // The stager reads the segment and never takes the GIL: stop and join it
+    // before the unmap below.
+    stager_.reset();
     terminate_.store(true);
     if (runnerThread_.joinable()) {
       // The runner thread re-acquires the GIL between queue waits; joining
@@ -267,6 +273,11 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
     if (!a.device().is_cpu()) a = a.to(at::kCPU);
     a = a.to(at::kLong).contiguous();
     if (a.numel() != batchSize_) throw RpcError("envpool: action size mismatch");
+    if (stager_) {
+      // (before the work is posted: a refused submit must leave nothing queued)
+      std::string err = stager_->submit(b);
+      if (!err.empty()) throw RpcError(err);
+    }
     std::memcpy(actions() + b * batchSize_, a.data_ptr<int64_t>(), sizeof(int64_t) * batchSize_);
     for (int w = 0; w < numWorkers_; ++w) {
       WorkerQueue* q = queue(w);
@@ -275,12 +286,14 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
       q->tail.store(t + 1, std::memory_order_release);
       sem_post(&q->itemsSem);
     }
+    inFlight_[b].store(true, std::memory_order_relaxed);
   }
 
   // Non-consuming completion check: true iff every worker has posted batch
   // b's completion semaphore (result(b) would return without blocking).
   bool poll(int b) {
     if (b < 0 || b >= numBatches_) return false;
+    if (stager_) return stager_->ready(b);
     for (int w = 0; w < numWorkers_; ++w) {
       int v = 0;
       if (sem_getvalue(&doneSems()[b * numWorkers_ + w], &v) != 0 || v < 1) return false;
@@ -289,6 +302,19 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
   }
 
   py::object result(int b) {
+    if (stager_) {
+      if (b < 0 || b >= numBatches_) throw RpcError("envpool: bad batch index");
+      std::string err;
+      int slot;
+      {
+        py::gil_scoped_release rel;
+        slot = stager_->wait(b, &err);
+      }
+      if (slot < 0) throw RpcError(err);
+      inFlight_[b].store(false, std::memory_order_relaxed);
+      lastSlot_[b] = slot;
+      return slotDicts_[b][slot];
+    }
     {
       py::gil_scoped_release rel;
       for (int w = 0; w < numWorkers_; ++w) {
@@ -304,8 +330,90 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
       }
       checkFailureNoGil();
     }
+    inFlight_[b].store(false, std::memory_order_relaxed);
     if (!tensorsBuilt_) buildTensors();
     return batchDicts_[b];
+  }
+
+  // ------------------------------------------------------------- staging
+
+  // slots[b][s] is a dict field -> CPU tensor shaped like result(b)'s views.
+  // From here on a native thread copies every finished batch into the next
+  // slot of its batch (see stager.h); poll/result speak about that copy.
+  void enableStaging(py::object slots) {
+    if (attached_) throw RpcError("envpool: staging belongs to the pool's owner");
+    if (stager_) throw RpcError("envpool: staging is already enabled");
+    for (int b = 0; b < numBatches_; ++b) {
+      if (inFlight_[b].load()) {
+        throw RpcError("envpool: enable_staging with batch " + std::to_string(b) +
+                       " in flight; consume its result first");
+      }
+    }
+    auto perBatch = py::cast<py::list>(slots);
+    if (static_cast<int>(perBatch.size()) != numBatches_) {
+      throw RpcError("envpool: enable_staging needs one slot list per batch");
+    }
+    std::vector<std::vector<py::object>> dicts(numBatches_);
+    std::vector<std::vector<std::vector<SlotField>>> fields(numBatches_);
+    size_t numSlots = 0;
+    for (int b = 0; b < numBatches_; ++b) {
+      auto perSlot = py::cast<py::list>(perBatch[b]);
+      if (b == 0) numSlots = perSlot.size();
+      if (perSlot.size() < 2 || perSlot.size() != numSlots) {
+        throw RpcError("envpool: every batch needs the same number (>= 2) of staging slots");
+      }
+      for (py::handle sl : perSlot) {
+        auto d = py::cast<py::dict>(sl);
+        std::vector<SlotField> fs;
+        for (auto item : d) {
+          SlotField f;
+          f.name = py::cast<std::string>(item.first);
+          f.tensor = py::cast<at::Tensor>(item.second);
+          if (!f.tensor.device().is_cpu() || !f.tensor.is_contiguous()) {
+            throw RpcError("envpool: staging slot field '" + f.name +
+                           "' must be a contiguous CPU tensor");
+          }
+          fs.push_back(std::move(f));
+        }
+        fields[b].push_back(std::move(fs));
+        dicts[b].push_back(py::reinterpret_borrow<py::object>(sl));
+      }
+    }
+    slotDicts_ = std::move(dicts);
+    slotFields_ = std::move(fields);
+    lastSlot_.assign(numBatches_, -1);
+
+    StagerConfig cfg;
+    cfg.numWorkers = numWorkers_;
+    cfg.batchSize = batchSize_;
+    cfg.numBatches = numBatches_;
+    cfg.numSlots = static_cast<int>(numSlots);
+    cfg.doneSems = doneSems();
+    cfg.prepare = [this](StagerPlan& plan) { return planStaging(plan); };
+    cfg.failure = [this]() -> std::string {
+      try {
+        checkFailureNoGil();
+        checkChildrenAliveNoGil();
+      } catch (const std::exception& e) {
+        return e.what();
+      }
+      return "";
+    };
+    stager_ = std::make_unique<Stager>(std::move(cfg));
+  }
+
+  bool stagingEnabled() const { return stager_ != nullptr; }
+
+  int stagedSlot(int b) {
+    if (!stager_) throw RpcError("envpool: staging is not enabled");
+    if (b < 0 || b >= numBatches_) throw RpcError("envpool: bad batch index");
+    return lastSlot_[b];
+  }
+
+  void release(int b, int slot) {
+    if (!stager_) throw RpcError("envpool: staging is not enabled");
+    std::string err = stager_->release(b, slot);
+    if (!err.empty()) throw RpcError(err);
   }
 
   at::Tensor dataRegion() {
@@ -355,6 +463,49 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
         throw RpcError("envpool worker " + std::to_string(i) + " died");
       }
     }
+  }
+
+  // Stager thread, no GIL, once: a worker has posted, so the layout is
+  // published. Match every slot's tensors against it.
+  std::string planStaging(StagerPlan& plan) {
+    Header* h = header();
+    if (h->layoutReady.load(std::memory_order_acquire) == 0) {
+      return "envpool: a worker finished before the field layout was published";
+    }
+    plan.assign(numBatches_, {});
+    for (int b = 0; b < numBatches_; ++b) {
+      for (const std::vector<SlotField>& slot : slotFields_[b]) {
+        if (slot.size() != h->numFields) {
+          return "envpool: a staging slot has " + std::to_string(slot.size()) +
+                 " fields, the env results have " + std::to_string(h->numFields);
+        }
+        std::vector<StagerCopy> copies;
+        for (uint32_t fi = 0; fi < h->numFields; ++fi) {
+          const FieldDesc& f = h->fields[fi];
+          const SlotField* sf = nullptr;
+          for (const SlotField& c : slot) {
+            if (c.name == f.name) sf = &c;
+          }
+          if (sf == nullptr) {
+            return std::string("envpool: staging slot lacks field '") + f.name + "'";
+          }
+          bool ok = sf->tensor.scalar_type() == wireToDtype(f.dtype) &&
+                    sf->tensor.dim() == f.ndim + 1 && sf->tensor.size(0) == batchSize_;
+          for (int i = 0; ok && i < f.ndim; ++i) ok = sf->tensor.size(i + 1) == f.shape[i];
+          if (!ok) {
+            return std::string("envpool: staging slot field '") + f.name +
+                   "' differs from the result's shape or dtype";
+          }
+          StagerCopy c;
+          c.src = fieldPtr(f, b);
+          c.dst = static_cast<char*>(sf->tensor.data_ptr());
+          c.bytesPerEnv = f.bytesPerEnv;
+          copies.push_back(c);
+        }
+        plan[b].push_back(std::move(copies));
+      }
+    }
+    return "";
   }
 
   void buildTensors() {
@@ -578,6 +729,17 @@ class EnvPoolImpl : public std::enable_shared_from_this<EnvPoolImpl> {
   int shmFd_ = -1;
   std::atomic<bool> terminate_{false};
   std::thread runnerThread_;
+  // step() may run on a dispatcher thread while the consumer polls
+  std::unique_ptr<std::atomic<bool>[]> inFlight_;
+  // native staging (enableStaging): off unless asked for
+  struct SlotField {
+    std::string name;
+    at::Tensor tensor;
+  };
+  std::vector<std::vector<py::object>> slotDicts_;              // [batch][slot]
+  std::vector<std::vector<std::vector<SlotField>>> slotFields_;  // [batch][slot][field]
+  std::vector<int> lastSlot_;
+  std::unique_ptr<Stager> stager_;
 };
 
 // ------------------------------------------------------------- wrappers
@@ -615,6 +777,12 @@ EnvStepperFuture EnvPool::step(int batchIndex, py::object action) {
 }
 
 bool EnvPool::poll(int batchIndex) { return impl_->poll(batchIndex); }
+
+py::object EnvPool::result(int batchIndex) { return impl_->result(batchIndex); }
+void EnvPool::enableStaging(py::object slots) { impl_->enableStaging(std::move(slots)); }
+bool EnvPool::stagingEnabled() { return impl_->stagingEnabled(); }
+int EnvPool::stagedSlot(int batchIndex) { return impl_->stagedSlot(batchIndex); }
+void EnvPool::release(int batchIndex, int slot) { impl_->release(batchIndex, slot); }
 
 at::Tensor EnvPool::sharedBuffer() { return impl_->dataRegion(); }
 bool EnvPool::running() { return impl_->anyAlive(); }

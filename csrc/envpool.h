@@ -51,6 +51,18 @@ class EnvPool {
   ~EnvPool();
   EnvStepperFuture step(int batchIndex, py::object action);
   bool poll(int batchIndex);  // true iff result(batchIndex) would not block
+  py::object result(int batchIndex);  // what the step's future returns
+  // Native staging (csrc/stager.h). slots[b][s] is a dict of contiguous CPU
+  // tensors shaped like result(b)'s views, at least two per batch. Valid with
+  // no batch in flight. From then on a native thread copies each finished
+  // batch into its slots in ping-pong order; poll(b) is true iff batch b is
+  // staged or failed, result(b) returns the slot's dict, stagedSlot(b) the
+  // index of that slot, and release(b, slot) lets the thread write it again.
+  // Never enabled: results are zero-copy views of the segment, as before.
+  void enableStaging(py::object slots);
+  bool stagingEnabled();
+  int stagedSlot(int batchIndex);
+  void release(int batchIndex, int slot);
   at::Tensor sharedBuffer();
   bool running();
   int numWorkersAlive();

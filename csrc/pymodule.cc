@@ -649,6 +649,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("step", &EnvPool::step, py::arg("batch_index"), py::arg("action"))
       .def("poll", &EnvPool::poll, py::arg("batch_index"),
            "true iff result(batch_index) would return without blocking")
+      .def("result", &EnvPool::result, py::arg("batch_index"))
+      .def("enable_staging", &EnvPool::enableStaging, py::arg("slots"),
+           "slots[batch][slot] = dict of contiguous CPU tensors shaped like the "
+           "results; a native thread then stages every finished batch into them")
+      .def("staging_enabled", &EnvPool::stagingEnabled)
+      .def("staged_slot", &EnvPool::stagedSlot, py::arg("batch_index"),
+           "slot index of the last result(batch_index)")
+      .def("release", &EnvPool::release, py::arg("batch_index"), py::arg("slot"),
+           "hand a consumed staging slot back to the stager")
       .def("shared_buffer", &EnvPool::sharedBuffer)
       .def("running", &EnvPool::running)
       .def("num_workers_alive", &EnvPool::numWorkersAlive);

@@ -102,9 +102,14 @@ class ImpalaConfig:
     #   9/9 stable and costs only ~2%. Re-enable with
     #   MOOLIB_AMD_FORCE_SIDE_STREAM=1 to investigate (round 2).
     prefetch_h2d: bool = True        # DMA env results to HBM on a copy stream as soon as
-    #   the workers finish (poll + persistent device buffers + events), so the
-    #   ~2 ms/step of frame H2D overlaps learner/actor compute instead of
-    #   serializing in the act loop.
+    #   they are staged (poll + persistent device buffers + events). The
+    #   pool's native stager thread (csrc/stager.h) copies each finished batch
+    #   out of the pageable shared-memory segment into pinned ping-pong slots
+    #   without the GIL, so the H2D issued here is a truly asynchronous DMA
+    #   and the act loop's thread no longer pays the ~1 ms/step the runtime
+    #   spent staging pageable frames on it (docs/ENVPOOL_STAGING.md).
+    #   MOOLIB_AMD_NO_NATIVE_STAGING=1 restores copies straight from the
+    #   segment's views.
     max_learn_backlog: int = 4       # stop acting when this many learn batches are queued
     group_timeout: float = 10.0      # broker eviction / allreduce timeout (seconds)
     bf16_weights: bool = True        # forward on bf16 shadow weights (fp32 master for optimizer/sync):
@@ -138,6 +143,10 @@ class EnvBatchState:
         self.prefetched = None       # cpu result dict already consumed from the future
         self.h2d_event = None        # recorded on the copy stream after staging
         self.consumed_event = None   # recorded on the compute stream after last read
+        # native staging: (slot, event of its H2D) the pool's stager gets back
+        # once that copy has completed
+        self.slot_events = None
+        self.unreleased = None
 
     def update(self, env_outputs, action, stats):
         # prev_action is a persistent device buffer (stable address for
@@ -423,6 +432,12 @@ class ImpalaPeer:
             )
             else None
         )
+        # Native staging needs the results' shapes, so it is switched on
+        # after the first result (_enable_native_staging).
+        self._want_native_staging = self._h2d_stream is not None and not os.environ.get(
+            "MOOLIB_AMD_NO_NATIVE_STAGING"
+        )
+        self._native_staging = False
         self._shm_registered = False
         if self.is_cuda and cfg.shm_host_register:
             try:
@@ -807,9 +822,28 @@ class ImpalaPeer:
             return
         cpu_out = st.future.result()  # poll() said this returns immediately
         st.future = None
-        if st.h2d_event is None:
+        self._issue_h2d(cur, st, cpu_out)
+        st.prefetched = cpu_out
+
+    def _issue_h2d(self, cur, st, cpu_out):
+        """Copy one env result into the batch's persistent device buffers on
+        the copy stream and record h2d_event behind the copies."""
+        if st.consumed_event is None:
             st.h2d_event = torch.cuda.Event()
             st.consumed_event = torch.cuda.Event()
+        if self._native_staging:
+            # cpu_out is a pinned slot the stager filled. The slot of the
+            # previous result goes back to it once its copy has landed (its
+            # CPU readers, EnvBatchState.update, ran before this batch was
+            # stepped again).
+            if st.unreleased is not None:
+                slot, ev = st.unreleased
+                if not ev.query():
+                    ev.synchronize()
+                self.envs.release(cur, slot)
+            slot = self.envs.staged_slot(cur)
+            st.h2d_event = st.slot_events[slot]
+            st.unreleased = (slot, st.h2d_event)
         # Don't overwrite buffers the compute stream may still be reading.
         self._h2d_stream.wait_event(st.consumed_event)
         with torch.cuda.stream(self._h2d_stream):
@@ -821,7 +855,22 @@ class ImpalaPeer:
             for k, t in cpu_out.items():
                 st.staged[k].copy_(t, non_blocking=True)
             st.h2d_event.record()
-        st.prefetched = cpu_out
+
+    def _enable_native_staging(self, cpu_out):
+        """Hand the pool two pinned slots per actor batch, shaped like the
+        result just consumed. Only valid with no batch in flight, which holds
+        after the very first result; otherwise the shm views stay in use."""
+        self._want_native_staging = False
+        if any(s.future is not None or s.prefetched is not None for s in self.env_states):
+            return
+        slots = [
+            [{k: torch.empty_like(t).pin_memory() for k, t in cpu_out.items()} for _ in range(2)]
+            for _ in self.env_states
+        ]
+        self.envs.enable_staging(slots)
+        for st in self.env_states:
+            st.slot_events = [torch.cuda.Event() for _ in range(2)]
+        self._native_staging = True
 
     def act_once(self):
         cfg = self.cfg
@@ -837,6 +886,13 @@ class ImpalaPeer:
             env_state.prefetched = None
         else:
             cpu_env_outputs = env_state.future.result()
+            env_state.future = None
+            if self._native_staging:
+                # a pinned slot: same copy-stream path as a prefetched result
+                self._issue_h2d(cur, env_state, cpu_env_outputs)
+                prefetched = True
+            elif self._want_native_staging:
+                self._enable_native_staging(cpu_env_outputs)
         t0 = self._t("act_env_wait", t0)
         stream_ctx = (
             torch.cuda.stream(self.actor_stream)
@@ -906,7 +962,6 @@ class ImpalaPeer:
         t0 = self._t("act_batch", t0)
 
         env_state.update(cpu_env_outputs, action, self.stats)
-        del cpu_env_outputs  # aliases shm; next step() overwrites it
         env_state.future = self.envs.step(cur, action)
         self.stats["env_act_steps"] += action.numel()
         t0 = self._t("act_stats_step", t0)
