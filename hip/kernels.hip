@@ -408,6 +408,7 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 #include "wgrad3x3.hip.inc"
 #include "lstm.hip.inc"
 #include "lstm_wide.hip.inc"
+#include "lstm_input.hip.inc"
 #include "r2d2.hip.inc"
 
 // ------------------------------------------------------------ wrappers
@@ -608,6 +609,167 @@ std::vector<at::Tensor> lstm_wide_bwd(at::Tensor gates, at::Tensor cs, at::Tenso
   else
     lstmWideBwdLaunch<512>(gates, cs, c0, notdone, dH, dhT, dcT, whhPackedN, dG, dh0, dc0);
   return {dG, dh0, dc0};
+}
+
+// ---- fused LSTM input projection (lstm_input.hip.inc)
+
+static int lstmInputRealKind(const at::Tensor& t, const char* who, const char* name) {
+  switch (t.scalar_type()) {
+    case at::kFloat: return lstm_input::kRealF32;
+    case at::kBFloat16: return lstm_input::kRealBF16;
+    case at::kHalf: return lstm_input::kRealF16;
+    case at::kDouble: return lstm_input::kRealF64;
+    default: TORCH_CHECK(false, who, ": ", name, " must be floating point, got ", t.scalar_type());
+  }
+}
+
+static int lstmInputIntKind(const at::Tensor& t, const char* who, const char* name) {
+  switch (t.scalar_type()) {
+    case at::kByte: return lstm_input::kIntU8;
+    case at::kChar: return lstm_input::kIntI8;
+    case at::kShort: return lstm_input::kIntI16;
+    case at::kInt: return lstm_input::kIntI32;
+    case at::kLong: return lstm_input::kIntI64;
+    default: TORCH_CHECK(false, who, ": ", name, " must be an integer tensor, got ", t.scalar_type());
+  }
+}
+
+struct LstmInputShape {
+  int M, N, K, A;
+  lstm_input::RowInputs rows;
+};
+
+// Everything the kernels index by: feat [M,256] bf16, reward / prev_action
+// [M], weight_ih [4H, 257+A] fp32 or bf16, all contiguous on feat's device.
+static LstmInputShape checkLstmInput(const at::Tensor& feat, const at::Tensor& reward,
+                                     const at::Tensor& action, const at::Tensor& W,
+                                     const char* who) {
+  TORCH_CHECK(feat.is_cuda() && feat.dim() == 2 && feat.scalar_type() == at::kBFloat16, who,
+              ": feat must be a [M, 256] bf16 CUDA tensor, got ", feat.scalar_type(), " ",
+              feat.sizes());
+  TORCH_CHECK(feat.size(1) == lstm_input::kF, who, ": feature width must be ", lstm_input::kF,
+              ", got ", feat.size(1));
+  TORCH_CHECK(feat.size(0) >= 1 && feat.size(0) <= (1 << 24), who, ": M must be 1 to 2^24 rows");
+  TORCH_CHECK(feat.is_contiguous() && reinterpret_cast<uintptr_t>(feat.data_ptr()) % 16 == 0, who,
+              ": feat must be contiguous and 16-byte aligned");
+  TORCH_CHECK(W.is_cuda() && W.device() == feat.device() && W.dim() == 2 &&
+                  (W.scalar_type() == at::kFloat || W.scalar_type() == at::kBFloat16),
+              who, ": weight_ih must be a [4H, 257+A] fp32 or bf16 tensor on feat's device");
+  TORCH_CHECK(W.is_contiguous(), who, ": weight_ih must be contiguous");
+  LstmInputShape s;
+  s.M = feat.size(0);
+  const int64_t N = W.size(0), A = W.size(1) - lstm_input::kF - 1;
+  TORCH_CHECK(N == 512 || N == 1024 || N == 2048, who,
+              ": hidden size must be 128, 256 or 512, got weight_ih ", W.sizes());
+  TORCH_CHECK(A >= 1 && A <= lstm_input::kMaxActions, who, ": 1 to ", lstm_input::kMaxActions,
+              " actions are served, weight_ih ", W.sizes(), " has ", A);
+  s.N = N;
+  s.A = A;
+  s.K = W.size(1);
+  for (const at::Tensor* t : {&reward, &action})
+    TORCH_CHECK(t->is_cuda() && t->device() == feat.device() && t->dim() == 1 &&
+                    t->size(0) == s.M && t->is_contiguous(),
+                who, ": reward and prev_action must be contiguous [M] tensors on feat's device");
+  s.rows.reward = reward.data_ptr();
+  s.rows.action = action.data_ptr();
+  s.rows.rewardKind = lstmInputRealKind(reward, who, "reward");
+  s.rows.actionKind = lstmInputIntKind(action, who, "prev_action");
+  return s;
+}
+
+template <typename WT>
+static void lstmInputFwdLaunch(const LstmInputShape& s, const at::Tensor& feat, const at::Tensor& W,
+                               const at::Tensor& biasIh, const at::Tensor& biasHh, int biasKind,
+                               at::Tensor& Xg) {
+  using bf16 = lstm::bf16;
+  auto stream = c10::hip::getCurrentHIPStream();
+  auto launch = [&](auto rt) {
+    constexpr int RT = decltype(rt)::value;
+    dim3 grid((s.M + RT * 16 - 1) / (RT * 16), s.N / lstm_input::kBN);
+    hipLaunchKernelGGL((lstm_input::fwd_kernel<WT, RT>), grid, dim3(lstm_input::kThreads), 0,
+                       stream, reinterpret_cast<const bf16*>(feat.data_ptr()), s.rows,
+                       reinterpret_cast<const WT*>(W.data_ptr()), biasIh.data_ptr(),
+                       biasHh.data_ptr(), biasKind, reinterpret_cast<bf16*>(Xg.data_ptr()), s.M,
+                       s.N, s.A);
+  };
+  if (s.M < 1024)
+    launch(std::integral_constant<int, 2>());
+  else
+    launch(std::integral_constant<int, 4>());
+}
+
+at::Tensor lstm_input_fwd(at::Tensor feat, at::Tensor reward, at::Tensor action, at::Tensor W,
+                          at::Tensor biasIh, at::Tensor biasHh) {
+  const char* who = "lstm input fwd";
+  LstmInputShape s = checkLstmInput(feat, reward, action, W, who);
+  const int biasKind = lstmInputRealKind(biasIh, who, "bias_ih");
+  TORCH_CHECK(biasHh.defined() && biasHh.scalar_type() == biasIh.scalar_type(), who,
+              ": bias_ih and bias_hh must have one dtype");
+  checkLstmArg(biasIh, feat, biasIh.scalar_type(), {s.N}, who, "bias_ih");
+  checkLstmArg(biasHh, feat, biasIh.scalar_type(), {s.N}, who, "bias_hh");
+  auto Xg = at::empty({s.M, s.N}, feat.options());
+  if (W.scalar_type() == at::kFloat)
+    lstmInputFwdLaunch<float>(s, feat, W, biasIh, biasHh, biasKind, Xg);
+  else
+    lstmInputFwdLaunch<lstm::bf16>(s, feat, W, biasIh, biasHh, biasKind, Xg);
+  return Xg;
+}
+
+template <typename WT>
+static void lstmInputDgradLaunch(const LstmInputShape& s, const at::Tensor& dXg,
+                                 const at::Tensor& W, at::Tensor& dFeat) {
+  using bf16 = lstm::bf16;
+  auto stream = c10::hip::getCurrentHIPStream();
+  auto launch = [&](auto rt) {
+    constexpr int RT = decltype(rt)::value;
+    dim3 grid((s.M + RT * 16 - 1) / (RT * 16), lstm_input::kF / lstm_input::kBN);
+    hipLaunchKernelGGL((lstm_input::dgrad_kernel<WT, RT>), grid, dim3(lstm_input::kThreads), 0,
+                       stream, reinterpret_cast<const bf16*>(dXg.data_ptr()),
+                       reinterpret_cast<const WT*>(W.data_ptr()),
+                       reinterpret_cast<bf16*>(dFeat.data_ptr()), s.M, s.N, s.K);
+  };
+  if (s.M < 1024)
+    launch(std::integral_constant<int, 2>());
+  else
+    launch(std::integral_constant<int, 4>());
+}
+
+// Returns (d_feat [M,256] bf16 or an undefined tensor, dW_ih [4H, 257+A] fp32,
+// db [4H] fp32, the gradient of either bias).
+std::vector<at::Tensor> lstm_input_bwd(at::Tensor dXg, at::Tensor feat, at::Tensor reward,
+                                       at::Tensor action, at::Tensor W, bool needFeat) {
+  const char* who = "lstm input bwd";
+  LstmInputShape s = checkLstmInput(feat, reward, action, W, who);
+  checkLstmArg(dXg, feat, at::kBFloat16, {s.M, s.N}, who, "dXg");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dXg.data_ptr()) % 16 == 0, who,
+              ": dXg must be 16-byte aligned");
+  using bf16 = lstm::bf16;
+  auto stream = c10::hip::getCurrentHIPStream();
+  at::Tensor dFeat;
+  if (needFeat) {
+    dFeat = at::empty_like(feat);
+    if (W.scalar_type() == at::kFloat)
+      lstmInputDgradLaunch<float>(s, dXg, W, dFeat);
+    else
+      lstmInputDgradLaunch<bf16>(s, dXg, W, dFeat);
+  }
+  auto fopts = feat.options().dtype(at::kFloat);
+  const int slabs = (s.M + lstm_input::kSlab - 1) / lstm_input::kSlab;
+  const int nCT = lstm_input::kF / 16 + (s.A + 2 + 15) / 16;
+  auto ws = at::empty({slabs, s.N, nCT * 16}, fopts);
+  auto dW = at::empty({s.N, s.K}, fopts);
+  auto db = at::empty({s.N}, fopts);
+  hipLaunchKernelGGL(lstm_input::wgrad_kernel, dim3(s.N / lstm_input::kBN, slabs),
+                     dim3(lstm_input::kThreads), 0, stream,
+                     reinterpret_cast<const bf16*>(dXg.data_ptr()),
+                     reinterpret_cast<const bf16*>(feat.data_ptr()), s.rows,
+                     ws.data_ptr<float>(), s.M, s.N, s.A, nCT);
+  const int64_t outs = (int64_t)s.N * (s.K + 1);
+  hipLaunchKernelGGL(lstm_input::wgrad_reduce_kernel,
+                     dim3((outs + lstm_input::kThreads - 1) / lstm_input::kThreads),
+                     dim3(lstm_input::kThreads), 0, stream, ws.data_ptr<float>(),
+                     dW.data_ptr<float>(), db.data_ptr<float>(), slabs, s.N, s.K, nCT * 16);
+  return {dFeat, dW, db};
 }
 
 std::vector<at::Tensor> vtrace_from_log_rhos(at::Tensor log_rhos, at::Tensor discounts,
@@ -1321,6 +1483,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_wide_fwd", &lstm_wide_fwd,
         "register-resident masked LSTM scan fwd, hidden 128/512; save=False is forward-only");
   m.def("lstm_wide_bwd", &lstm_wide_bwd, "register-resident masked LSTM scan bwd, hidden 128/512");
+  m.def("lstm_input_fwd", &lstm_input_fwd,
+        "fused LSTM input projection: feat @ W_ih[:, :256]^T + clamped reward column + gathered "
+        "action column + biases, W_ih in nn.LSTM's layout (gfx950)");
+  m.def("lstm_input_bwd", &lstm_input_bwd,
+        "fused LSTM input projection bwd: d_feat, dW_ih and the bias gradient, deterministic");
+  m.attr("LSTM_INPUT_MAX_ACTIONS") = lstm_input::kMaxActions;  // widest action set served
   m.def("vtrace_from_log_rhos", &vtrace_from_log_rhos, "fused V-trace scan (gfx950)");
   m.def("impala_loss", &impala_loss, "fused IMPALA loss fwd+grad (gfx950)");
   m.def("r2d2_loss", &r2d2_loss,

@@ -24,6 +24,8 @@ call (the MOOLIB_AMD_* switches may change between two forwards):
 | section, plain | otherwise | `nn.Conv2d`, pool, blocks as plain modules |
 | block in `forward_fused` | no grad and `conv3x3.runs_on_mfma` | two fused MFMA conv launches |
 | block in `forward_fused` | otherwise | `bias_relu`/relu, conv, `bias_relu`, conv, `bias_add2` |
+| core input | `fused_core_input=True`, the fused-scan branch is taken and `lstm_ops.core_input_available` | `lstm_ops.core_input_projection` on `relu(fc(x))`, reward, prev_action and the core's own `weight_ih_l0` and biases: no one_hot, clamp, cat or `F.linear` |
+| core input | otherwise | one_hot, clamp, cat; on the fused-scan branch `F.linear` over all T |
 
 A bias-free conv is the MFMA kernel when `conv3x3.runs_on_mfma`, else
 F.conv2d (MIOpen). tests/test_trunk_routes.py pins the launches of each row.
@@ -123,10 +125,13 @@ class ConvSection(nn.Module):
 
 
 class AtariNet(nn.Module):
-    def __init__(self, num_actions=18, input_channels=4, use_lstm=False, lstm_size=256):
+    def __init__(self, num_actions=18, input_channels=4, use_lstm=False, lstm_size=256,
+                 fused_core_input=False):
         super().__init__()
         self.num_actions = num_actions
         self.use_lstm = use_lstm
+        # opt-in route, no module or parameter of its own (see the route table)
+        self.fused_core_input = fused_core_input
 
         chans = [16, 32, 32]
         sections = []
@@ -203,25 +208,46 @@ class AtariNet(nn.Module):
         x = x.reshape(T * B, -1)
         x = F.relu(self.fc(x))
 
-        prev_action_onehot = F.one_hot(
-            inputs["prev_action"].view(T * B).to(torch.int64), self.num_actions
-        ).to(x.dtype)
-        clipped_reward = reward.view(T * B, 1).clamp(-1, 1).to(x.dtype)
-        core_input = torch.cat([x, clipped_reward, prev_action_onehot], dim=-1)
+        fused_scan = (
+            self.use_lstm
+            and lstm_ops.available(self.core.hidden_size, x.device)
+            and (torch.is_autocast_enabled() or x.dtype == torch.bfloat16)
+        )
+        Xg = None
+        if (
+            fused_scan
+            and self.fused_core_input
+            and x.dtype == torch.bfloat16
+            and lstm_ops.core_input_available(
+                x.size(1), self.num_actions, self.core.hidden_size, x.device
+            )
+        ):
+            # the whole front end of the core in one launch, from the core's
+            # own parameters: no one_hot, clamp, cat, bias add or weight cast
+            Xg = lstm_ops.core_input_projection(
+                x, reward.reshape(T * B), inputs["prev_action"].reshape(T * B),
+                self.core.weight_ih_l0, self.core.bias_ih_l0, self.core.bias_hh_l0,
+            ).view(T, B, -1)
+        else:
+            prev_action_onehot = F.one_hot(
+                inputs["prev_action"].view(T * B).to(torch.int64), self.num_actions
+            ).to(x.dtype)
+            clipped_reward = reward.view(T * B, 1).clamp(-1, 1).to(x.dtype)
+            core_input = torch.cat([x, clipped_reward, prev_action_onehot], dim=-1)
 
         if self.use_lstm:
             done = inputs["done"]
-            core_input = core_input.view(T, B, -1)
-            if lstm_ops.available(self.core.hidden_size, core_input.device) and (
-                torch.is_autocast_enabled() or core_input.dtype == torch.bfloat16
-            ):
+            if Xg is None:
+                core_input = core_input.view(T, B, -1)
+            if fused_scan:
                 # fused MFMA sequence scan: one GEMM for x@W_ih over all T,
                 # one kernel for the masked recurrence (fwd and bwd each).
-                Xg = F.linear(
-                    core_input.reshape(T * B, -1),
-                    self.core.weight_ih_l0,
-                    self.core.bias_ih_l0 + self.core.bias_hh_l0,
-                ).view(T, B, -1).to(torch.bfloat16)
+                if Xg is None:
+                    Xg = F.linear(
+                        core_input.reshape(T * B, -1),
+                        self.core.weight_ih_l0,
+                        self.core.bias_ih_l0 + self.core.bias_hh_l0,
+                    ).view(T, B, -1).to(torch.bfloat16)
                 notdone_f = (~done).float()
                 h0 = core_state[0][0].to(torch.bfloat16)
                 c0 = core_state[1][0].float()
@@ -270,7 +296,9 @@ class AtariNet(nn.Module):
         return out, core_state
 
 
-def create_model(num_actions=18, use_lstm=False, device="cpu", lstm_size=256):
-    model = AtariNet(num_actions=num_actions, use_lstm=use_lstm, lstm_size=lstm_size)
+def create_model(num_actions=18, use_lstm=False, device="cpu", lstm_size=256,
+                 fused_core_input=False):
+    model = AtariNet(num_actions=num_actions, use_lstm=use_lstm, lstm_size=lstm_size,
+                     fused_core_input=fused_core_input)
     model.to(device)
     return model

@@ -16,13 +16,25 @@ one launch per direction, on one of two kernel families:
 
 Any other hidden size is not served here (`available` is False).
 notdone is 0 or 1; the kernels do not check it.
+
+`core_input_projection` is the front end of the same core as one op
+(hip/lstm_input.hip.inc): X = feat @ W_ih[:, :256]^T + the clamped reward times
+its column + the previous action's column + both biases, from weight_ih_l0 as
+nn.LSTM stores it. It replaces one_hot, clamp, cat, the bias add, the weight
+cast and an odd-K GEMM, forward and backward.
 """
 import os
 
 import torch
+import torch.nn.functional as F
 
 
 WIDE_SIZES = (128, 512)  # served by hip/lstm_wide.hip.inc; 256 by hip/lstm.hip.inc
+# core_input_projection on the GPU: the feature width and the widest action set
+# (_kernels.LSTM_INPUT_MAX_ACTIONS is the same number: the reward column, the
+# action columns and the bias column of the weight-gradient product fill 64)
+CORE_INPUT_FEATURES = 256
+CORE_INPUT_MAX_ACTIONS = 62
 
 
 def _kernels():
@@ -148,3 +160,80 @@ def fused_lstm_scan(X, notdone, h0, c0, w_hh):
         X.contiguous(), notdone.contiguous(), h0.contiguous(), c0.contiguous(), packed_t, False
     )
     return H, hT, cT
+
+
+def core_input_available(feat_width, num_actions, hidden_size, device):
+    """Whether core_input_projection runs its kernels for this shape on `device`."""
+    return (
+        feat_width == CORE_INPUT_FEATURES
+        and 1 <= num_actions <= CORE_INPUT_MAX_ACTIONS
+        and hidden_size in (256,) + WIDE_SIZES
+        and device.type == "cuda"
+        and _kernels() is not None
+    )
+
+
+def core_input_eager(feat, reward, prev_action, weight_ih, bias_ih, bias_hh):
+    """The projection in plain torch, in feat's dtype: what the kernels compute,
+    as AtariNet wrote it before them (one_hot, clamp, cat, F.linear). An action
+    outside [0, A) gives an all-zero one-hot row."""
+    A = weight_ih.shape[1] - feat.shape[1] - 1
+    action = prev_action.reshape(-1).to(torch.int64)
+    valid = ((action >= 0) & (action < A)).unsqueeze(-1)
+    onehot = F.one_hot(action.clamp(0, A - 1), A).to(feat.dtype) * valid.to(feat.dtype)
+    clipped = reward.reshape(-1, 1).clamp(-1, 1).to(feat.dtype)
+    x = torch.cat([feat, clipped, onehot], dim=-1)
+    return F.linear(x, weight_ih.to(feat.dtype), (bias_ih + bias_hh).to(feat.dtype))
+
+
+class _CoreInputProjection(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, reward, prev_action, weight_ih, bias_ih, bias_hh):
+        Xg = _kernels().lstm_input_fwd(feat, reward, prev_action, weight_ih, bias_ih, bias_hh)
+        ctx.save_for_backward(feat, reward, prev_action, weight_ih)
+        return Xg
+
+    @staticmethod
+    def backward(ctx, dXg):
+        feat, reward, prev_action, weight_ih = ctx.saved_tensors
+        d_feat, dW, db = _kernels().lstm_input_bwd(
+            dXg.contiguous(), feat, reward, prev_action, weight_ih, ctx.needs_input_grad[0]
+        )
+        # dW and db are fp32; autograd casts them to the parameters' dtype
+        return d_feat, None, None, dW, db, db
+
+
+def core_input_projection(feat, reward, prev_action, weight_ih, bias_ih, bias_hh):
+    """feat [M,256] (relu(fc(x))); reward [M], not clipped; prev_action [M], any
+    integer dtype; weight_ih [4H, 257+A] in the model's column order (features,
+    reward, actions); bias_ih, bias_hh [4H]. Returns Xg [M,4H]:
+
+      Xg[m,n] = sum_k feat[m,k] W[n,k] + clamp(reward[m],-1,1) W[n,256]
+                + W[n,257+a_m] + bias_ih[n] + bias_hh[n]
+
+    On a GPU with _kernels built this is one launch (three more in the
+    backward): feat bf16, W fp32 or bf16 and rounded to bf16 as it is read,
+    fp32 accumulation with the reward in fp32, one rounding to the bf16 result.
+    H in (128, 256, 512), A <= CORE_INPUT_MAX_ACTIONS; anything else on a GPU
+    raises. Gradients: feat bf16, weight_ih and the biases fp32 (both biases
+    get the same vector), none for reward and prev_action; summed in a fixed
+    order. An action outside [0, A) contributes nothing. No host sync.
+    On the CPU, or without _kernels, core_input_eager runs."""
+    if not feat.is_cuda or _kernels() is None:
+        return core_input_eager(feat, reward, prev_action, weight_ih, bias_ih, bias_hh)
+    if feat.dim() != 2 or weight_ih.dim() != 2:
+        raise ValueError("core_input_projection: feat [M,256] and weight_ih [4H,257+A] expected")
+    A = weight_ih.shape[1] - feat.shape[1] - 1
+    if not core_input_available(feat.shape[1], A, weight_ih.shape[0] // 4, feat.device):
+        raise ValueError(
+            "core_input_projection: no kernel for feature width %d, %d actions, weight_ih %s "
+            "(width 256, 1..%d actions, hidden 128/256/512 are served)"
+            % (feat.shape[1], A, tuple(weight_ih.shape), CORE_INPUT_MAX_ACTIONS)
+        )
+    if feat.dtype != torch.bfloat16:
+        raise ValueError("core_input_projection: feat must be bf16 on the GPU, got %s" % feat.dtype)
+    if not weight_ih.is_contiguous():
+        raise ValueError("core_input_projection: weight_ih must be contiguous")
+    return _CoreInputProjection.apply(
+        feat.contiguous(), reward.contiguous(), prev_action.contiguous(), weight_ih, bias_ih, bias_hh
+    )
