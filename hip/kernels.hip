@@ -23,6 +23,9 @@
 //   act_categorical_kernel, act_eps_greedy_kernel (act.hip.inc) — the actor's
 //     action head: Philox4x32-10 sampling from a [seed, step] state on the
 //     device, one launch each.
+//   grad_kernel, pack_kernel (lstm_whh.hip.inc) — the LSTM's recurrent weight
+//     gradient on the MFMA with the time shift and the done-mask applied on
+//     load, and weight_hh_l0 packed for both scans in one launch.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <torch/extension.h>
@@ -409,6 +412,7 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 #include "lstm.hip.inc"
 #include "lstm_wide.hip.inc"
 #include "lstm_input.hip.inc"
+#include "lstm_whh.hip.inc"
 #include "r2d2.hip.inc"
 
 // ------------------------------------------------------------ wrappers
@@ -770,6 +774,91 @@ std::vector<at::Tensor> lstm_input_bwd(at::Tensor dXg, at::Tensor feat, at::Tens
                      dim3(lstm_input::kThreads), 0, stream, ws.data_ptr<float>(),
                      dW.data_ptr<float>(), db.data_ptr<float>(), slabs, s.N, s.K, nCT * 16);
   return {dFeat, dW, db};
+}
+
+// ---- recurrent weight gradient and W_hh pack (lstm_whh.hip.inc)
+
+static bool lstmWhhHidden(int64_t H) { return H == 128 || H == 256 || H == 512; }
+
+template <int H>
+static void lstmWhhGradLaunch(const at::Tensor& dG, const at::Tensor& Hs, const at::Tensor& h0,
+                              const at::Tensor& notdone, at::Tensor& dW) {
+  using G = lstm_whh::Geo<H>;
+  using bf16 = lstm::bf16;
+  const int B = dG.size(1), M = dG.size(0) * B;
+  const int slabs = (M + G::kSlab - 1) / G::kSlab;
+  auto stream = c10::hip::getCurrentHIPStream();
+  // a single slab writes dW itself; more write partials that the reduce sums
+  at::Tensor ws = slabs > 1 ? at::empty({slabs, 4 * H, H}, dW.options()) : dW;
+  hipLaunchKernelGGL((lstm_whh::grad_kernel<G::kWM, G::kWN>),
+                     dim3(H / G::kTJ, 4 * H / G::kTN, slabs), dim3(lstm_whh::kThreads), 0, stream,
+                     reinterpret_cast<const bf16*>(dG.data_ptr()),
+                     reinterpret_cast<const bf16*>(Hs.data_ptr()),
+                     reinterpret_cast<const bf16*>(h0.data_ptr()), notdone.data_ptr<float>(),
+                     ws.data_ptr<float>(), M, B, 4 * H, H, G::kSlab);
+  if (slabs > 1) {
+    const int n4 = 4 * H * H / 4;
+    hipLaunchKernelGGL(lstm_whh::grad_reduce_kernel,
+                       dim3((n4 + lstm_whh::kThreads - 1) / lstm_whh::kThreads),
+                       dim3(lstm_whh::kThreads), 0, stream,
+                       reinterpret_cast<const float4*>(ws.data_ptr<float>()),
+                       reinterpret_cast<float4*>(dW.data_ptr<float>()), slabs, n4);
+  }
+}
+
+// dW_hh [4H,H] fp32 = dG^T @ Hp, Hp[t] = notdone[t] != 0 ? (t == 0 ? h0 : H[t-1]) : 0
+at::Tensor lstm_whh_grad(at::Tensor dG, at::Tensor Hs, at::Tensor h0, at::Tensor notdone) {
+  const char* who = "lstm whh grad";
+  TORCH_CHECK(dG.is_cuda() && dG.dtype() == at::kBFloat16 && dG.dim() == 3, who,
+              ": dG [T,B,4H] bf16");
+  TORCH_CHECK(dG.is_contiguous(), who, ": dG must be contiguous");
+  const int64_t T = dG.size(0), B = dG.size(1), H = dG.size(2) / 4;
+  TORCH_CHECK(dG.size(2) == 4 * H && lstmWhhHidden(H), who,
+              ": hidden size must be 128, 256 or 512, got dG [", dG.sizes(), "]");
+  TORCH_CHECK(T > 0 && B > 0, who, ": empty sequence or batch");
+  TORCH_CHECK(T * B <= INT_MAX - 2 * lstm_whh::kKC, who, ": T*B too large");
+  checkLstmArg(Hs, dG, at::kBFloat16, {T, B, H}, who, "H");
+  checkLstmArg(h0, dG, at::kBFloat16, {B, H}, who, "h0");
+  checkLstmArg(notdone, dG, at::kFloat, {T, B}, who, "notdone");
+  for (const at::Tensor* t : {&dG, &Hs, &h0})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, who,
+                ": dG, H and h0 must be 16-byte aligned");
+  auto dW = at::empty({4 * H, H}, dG.options().dtype(at::kFloat));
+  if (H == 128)
+    lstmWhhGradLaunch<128>(dG, Hs, h0, notdone, dW);
+  else if (H == 256)
+    lstmWhhGradLaunch<256>(dG, Hs, h0, notdone, dW);
+  else
+    lstmWhhGradLaunch<512>(dG, Hs, h0, notdone, dW);
+  return dW;
+}
+
+// (pack_mfma_b(bf16(w)^T), pack_mfma_b(bf16(w))) of ops/lstm.py, from w [4H,H] as stored
+std::vector<at::Tensor> lstm_whh_pack(at::Tensor w) {
+  const char* who = "lstm whh pack";
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2, who, ": w [4H,H] on the GPU");
+  TORCH_CHECK(w.scalar_type() == at::kFloat || w.scalar_type() == at::kBFloat16, who,
+              ": w must be float32 or bfloat16, got ", w.scalar_type());
+  TORCH_CHECK(w.is_contiguous(), who, ": w must be contiguous");
+  const int64_t H = w.size(1);
+  TORCH_CHECK(w.size(0) == 4 * H && lstmWhhHidden(H), who,
+              ": hidden size must be 128, 256 or 512, got w [", w.sizes(), "]");
+  using bf16 = lstm::bf16;
+  auto opts = w.options().dtype(at::kBFloat16);
+  auto packedT = at::empty({4 * H * H}, opts);
+  auto packedN = at::empty({4 * H * H}, opts);
+  auto stream = c10::hip::getCurrentHIPStream();
+  const dim3 grid(H / 32, 4 * H / 32);
+  if (w.scalar_type() == at::kFloat)
+    hipLaunchKernelGGL(lstm_whh::pack_kernel<float>, grid, dim3(lstm_whh::kThreads), 0, stream,
+                       w.data_ptr<float>(), reinterpret_cast<bf16*>(packedT.data_ptr()),
+                       reinterpret_cast<bf16*>(packedN.data_ptr()), (int)H);
+  else
+    hipLaunchKernelGGL(lstm_whh::pack_kernel<bf16>, grid, dim3(lstm_whh::kThreads), 0, stream,
+                       reinterpret_cast<const bf16*>(w.data_ptr()),
+                       reinterpret_cast<bf16*>(packedT.data_ptr()),
+                       reinterpret_cast<bf16*>(packedN.data_ptr()), (int)H);
+  return {packedT, packedN};
 }
 
 std::vector<at::Tensor> vtrace_from_log_rhos(at::Tensor log_rhos, at::Tensor discounts,
@@ -1489,6 +1578,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_input_bwd", &lstm_input_bwd,
         "fused LSTM input projection bwd: d_feat, dW_ih and the bias gradient, deterministic");
   m.attr("LSTM_INPUT_MAX_ACTIONS") = lstm_input::kMaxActions;  // widest action set served
+  m.def("lstm_whh_grad", &lstm_whh_grad,
+        "dW_hh = dG^T @ shifted, masked H: MFMA slab partials + fixed-order reduce, no atomics");
+  m.def("lstm_whh_pack", &lstm_whh_pack,
+        "weight_hh_l0 -> (packed_t, packed_n), both scans' B-fragment layouts in one launch");
   m.def("vtrace_from_log_rhos", &vtrace_from_log_rhos, "fused V-trace scan (gfx950)");
   m.def("impala_loss", &impala_loss, "fused IMPALA loss fwd+grad (gfx950)");
   m.def("r2d2_loss", &r2d2_loss,

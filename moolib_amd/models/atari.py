@@ -26,6 +26,8 @@ call (the MOOLIB_AMD_* switches may change between two forwards):
 | block in `forward_fused` | otherwise | `bias_relu`/relu, conv, `bias_relu`, conv, `bias_add2` |
 | core input | `fused_core_input=True`, the fused-scan branch is taken and `lstm_ops.core_input_available` | `lstm_ops.core_input_projection` on `relu(fc(x))`, reward, prev_action and the core's own `weight_ih_l0` and biases: no one_hot, clamp, cat or `F.linear` |
 | core input | otherwise | one_hot, clamp, cat; on the fused-scan branch `F.linear` over all T |
+| core recurrent weight | `fused_core_recurrent=True` and the fused-scan branch is taken | `fused_lstm_scan(..., native_whh=True)`: one pack launch for `weight_hh_l0`, `lstm_ops.recurrent_weight_grad` for its gradient |
+| core recurrent weight | otherwise | bf16 cast, transpose and `pack_mfma_b` in torch; cat, mask multiply, fp32 casts and an fp32 GEMM in the backward |
 
 A bias-free conv is the MFMA kernel when `conv3x3.runs_on_mfma`, else
 F.conv2d (MIOpen). tests/test_trunk_routes.py pins the launches of each row.
@@ -126,12 +128,13 @@ class ConvSection(nn.Module):
 
 class AtariNet(nn.Module):
     def __init__(self, num_actions=18, input_channels=4, use_lstm=False, lstm_size=256,
-                 fused_core_input=False):
+                 fused_core_input=False, fused_core_recurrent=False):
         super().__init__()
         self.num_actions = num_actions
         self.use_lstm = use_lstm
-        # opt-in route, no module or parameter of its own (see the route table)
+        # opt-in routes, no module or parameter of their own (see the route table)
         self.fused_core_input = fused_core_input
+        self.fused_core_recurrent = fused_core_recurrent
 
         chans = [16, 32, 32]
         sections = []
@@ -252,7 +255,8 @@ class AtariNet(nn.Module):
                 h0 = core_state[0][0].to(torch.bfloat16)
                 c0 = core_state[1][0].float()
                 H, hT, cT = lstm_ops.fused_lstm_scan(
-                    Xg, notdone_f, h0, c0, self.core.weight_hh_l0
+                    Xg, notdone_f, h0, c0, self.core.weight_hh_l0,
+                    native_whh=self.fused_core_recurrent,
                 )
                 core_output = H.flatten(0, 1)
                 core_state = (
@@ -297,8 +301,9 @@ class AtariNet(nn.Module):
 
 
 def create_model(num_actions=18, use_lstm=False, device="cpu", lstm_size=256,
-                 fused_core_input=False):
+                 fused_core_input=False, fused_core_recurrent=False):
     model = AtariNet(num_actions=num_actions, use_lstm=use_lstm, lstm_size=lstm_size,
-                     fused_core_input=fused_core_input)
+                     fused_core_input=fused_core_input,
+                     fused_core_recurrent=fused_core_recurrent)
     model.to(device)
     return model

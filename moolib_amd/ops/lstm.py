@@ -22,6 +22,12 @@ notdone is 0 or 1; the kernels do not check it.
 its column + the previous action's column + both biases, from weight_ih_l0 as
 nn.LSTM stores it. It replaces one_hot, clamp, cat, the bias add, the weight
 cast and an odd-K GEMM, forward and backward.
+
+`fused_lstm_scan(..., native_whh=True)` puts what is left around weight_hh_l0
+on kernels too (hip/lstm_whh.hip.inc): `pack_whh` writes both packed layouts
+of the weight in one launch, and `recurrent_weight_grad` is the backward's
+dW_hh = dG^T @ (shifted, masked H) without the copy of H, the mask multiply,
+the fp32 casts and the fp32 GEMM.
 """
 import os
 
@@ -138,24 +144,108 @@ class _WideLSTMScan(torch.autograd.Function):
         return dG, None, dh0, dc0, dW
 
 
-def fused_lstm_scan(X, notdone, h0, c0, w_hh):
+def _native_whh(t):
+    return t.is_cuda and _kernels() is not None
+
+
+def pack_whh(w_hh):
+    """weight_hh_l0 [4H,H] -> (packed_t, packed_n): pack_mfma_b of bf16(w)^T
+    (the forward scan's B operand) and of bf16(w) (the backward's), bit for
+    bit. On a GPU with _kernels built, for an fp32 or bf16 weight, one launch
+    that reads the weight once (H in 128/256/512, anything else raises);
+    elsewhere the two pack_mfma_b calls."""
+    w = w_hh.detach()
+    if _native_whh(w) and w.dtype in (torch.float32, torch.bfloat16):
+        return tuple(_kernels().lstm_whh_pack(w.contiguous()))
+    w = w.to(torch.bfloat16)
+    return pack_mfma_b(w.t().contiguous()), pack_mfma_b(w.contiguous())
+
+
+def recurrent_weight_grad(dG, H, h0, notdone):
+    """dW_hh [4H,H] fp32 = dG^T @ Hp over all T*B rows, with
+    Hp[t] = where(notdone[t] != 0, h0 if t == 0 else H[t-1], 0).
+    dG [T,B,4H], H [T,B,H], h0 [B,H], notdone [T,B].
+
+    On a GPU with _kernels built: bf16 dG, H and h0, fp32 notdone, H in
+    128/256/512 (anything else raises); Hp is formed as the operand is
+    fetched, the product runs on the MFMA in fp32 and is summed in a fixed
+    order, so two calls agree bit for bit. No host sync. Elsewhere the same
+    in plain torch, in fp32."""
+    if _native_whh(dG):
+        return _kernels().lstm_whh_grad(
+            dG.contiguous(), H.contiguous(), h0.contiguous(), notdone.contiguous()
+        )
+    T, B, _ = dG.shape
+    prev = torch.cat([h0.unsqueeze(0), H[:-1]])
+    Hp = torch.where(notdone.unsqueeze(-1) != 0, prev, prev.new_zeros(()))
+    return dG.reshape(T * B, -1).t().float() @ Hp.reshape(T * B, -1).float()
+
+
+class _NativeWhhScan(torch.autograd.Function):
+    """Either kernel family's scan with weight_hh_l0 handled by pack_whh and
+    recurrent_weight_grad: packed_n is saved in place of the bf16 weight."""
+
+    @staticmethod
+    def forward(ctx, X, notdone, h0, c0, w_hh):
+        k = _kernels()
+        packed_t, packed_n = pack_whh(w_hh)
+        notdone, h0, c0 = notdone.contiguous(), h0.contiguous(), c0.contiguous()
+        if w_hh.shape[1] == 256:
+            H, gates, cs, hT, cT = k.lstm_fused_fwd(X.contiguous(), notdone, h0, c0, packed_t)
+        else:
+            H, gates, cs, hT, cT = k.lstm_wide_fwd(X.contiguous(), notdone, h0, c0, packed_t, True)
+        ctx.save_for_backward(gates, cs, c0, notdone, packed_n, h0, H)
+        return H, hT, cT
+
+    @staticmethod
+    def backward(ctx, dH, dhT, dcT):
+        k = _kernels()
+        gates, cs, c0, notdone, packed_n, h0, H = ctx.saved_tensors
+        empty = torch.Tensor()
+        bwd = k.lstm_fused_bwd if H.shape[2] == 256 else k.lstm_wide_bwd
+        dG, dh0, dc0 = bwd(
+            gates,
+            cs,
+            c0,
+            notdone,
+            dH.contiguous().to(torch.bfloat16),
+            dhT.contiguous().to(torch.bfloat16) if dhT is not None else empty,
+            dcT.contiguous().float() if dcT is not None else empty,
+            packed_n,
+        )
+        return dG, None, dh0, dc0, recurrent_weight_grad(dG, H, h0, notdone)
+
+
+def fused_lstm_scan(X, notdone, h0, c0, w_hh, native_whh=False):
     """X [T,B,4H] bf16; notdone [T,B] f32, 0 or 1; h0 [B,H] bf16; c0 [B,H] f32;
     w_hh [4H,H], with H in (128, 256, 512).
     Returns (H [T,B,H] bf16, hT [B,H] bf16, cT [B,H] f32).
 
     H == 256 runs the LDS-resident kernels. 128 and 512 run the register-
     resident ones, forward-only (nothing saved, plain tensors returned) when
-    grad mode is off or no input requires a gradient."""
+    grad mode is off or no input requires a gradient.
+
+    native_whh=True keeps the same scan kernels and moves everything else that
+    touches w_hh onto hip/lstm_whh.hip.inc: one pack launch in the forward
+    (its second output saved for the backward) and recurrent_weight_grad for
+    dW. All outputs and gradients but dW are bit-identical to the default; dW
+    differs by fp32 summation order only."""
     hidden = w_hh.shape[1]
-    if hidden == 256:
-        return _FusedLSTMScan.apply(X, notdone, h0, c0, w_hh)
-    if hidden not in WIDE_SIZES:
+    if hidden != 256 and hidden not in WIDE_SIZES:
         raise ValueError(
             "fused_lstm_scan: hidden size %d has no kernel (128, 256 and 512 do)" % hidden
         )
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (X, h0, c0, w_hh)):
+    wants_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (X, h0, c0, w_hh))
+    if native_whh and (hidden == 256 or wants_grad):
+        return _NativeWhhScan.apply(X, notdone, h0, c0, w_hh)
+    if hidden == 256:
+        return _FusedLSTMScan.apply(X, notdone, h0, c0, w_hh)
+    if wants_grad:
         return _WideLSTMScan.apply(X, notdone, h0, c0, w_hh)
-    packed_t = pack_mfma_b(w_hh.detach().to(torch.bfloat16).t().contiguous())
+    if native_whh:
+        packed_t = pack_whh(w_hh)[0]
+    else:
+        packed_t = pack_mfma_b(w_hh.detach().to(torch.bfloat16).t().contiguous())
     H, hT, cT = _kernels().lstm_wide_fwd(
         X.contiguous(), notdone.contiguous(), h0.contiguous(), c0.contiguous(), packed_t, False
     )
