@@ -408,6 +408,7 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 }  // namespace
 
 #include "conv3x3.hip.inc"
+#include "actor_section.hip.inc"
 #include "wgrad3x3.hip.inc"
 #include "lstm.hip.inc"
 #include "lstm_wide.hip.inc"
@@ -1565,6 +1566,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("w_packed"), py::arg("k"), py::arg("relu_in") = false,
         py::arg("bias_in") = py::none(), py::arg("epi") = 0, py::arg("bias1") = py::none(),
         py::arg("res") = py::none(), py::arg("bias2") = py::none(), py::arg("rt") = 0);
+  m.def("actor_section_nhwc", &actor_section_nhwc,
+        "actor trunk section after its conv in one launch: pool + two residual blocks, image "
+        "resident in LDS",
+        py::arg("u"), py::arg("pending_bias"), py::arg("packs"), py::arg("biases"),
+        py::arg("relu_out") = false);
+  m.attr("ACTOR_SECTION_LDS_MAX") = actor_section::kLdsMax;
   m.def("wgrad3x3_nhwc", &wgrad3x3_nhwc,
         "3x3/s1/p1 conv weight gradient on MFMA (row-slab LDS staging, gfx950)");
   m.def("lstm_fused_fwd", &lstm_fused_fwd, "fused masked LSTM sequence scan fwd (MFMA, gfx950)");

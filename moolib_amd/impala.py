@@ -84,6 +84,11 @@ class ImpalaConfig:
     #   step] state on the device) instead of torch.multinomial on a torch
     #   generator, so the captured actor graph registers no generator.
     #   MOOLIB_AMD_FUSED_SAMPLING=1 switches it on.
+    fused_actor_sections: bool = True  # actor forward: pool and both residual
+    #   blocks of each trunk section in ONE launch with the image resident in
+    #   LDS (ops.conv3x3.actor_section), 3 graph nodes where there were 15
+    #   and the same values bit for bit (docs/ACTOR_SECTION.md).
+    #   MOOLIB_AMD_NO_ACTOR_SECTION=1 switches it off.
     graph_learner: bool = False  # hipGraph-capture the learner fwd+bwd.
     #   OFF by default: replays of the captured learner (autograd backward
     #   incl. MIOpen bwd-weight convs) intermittently fault on ROCm 7.0
@@ -359,6 +364,9 @@ class ImpalaPeer:
             self.fwd_model = self.model
             self._master_params = []
             self._fwd_params = []
+        if hasattr(self.fwd_model, "fused_actor_sections"):
+            # a route of the no-grad forward only: the learner's is untouched
+            self.fwd_model.fused_actor_sections = cfg.fused_actor_sections
         if cfg.fused_optimizer:
             self._build_fused_optimizer()
         self.env_states = [

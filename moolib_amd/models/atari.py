@@ -22,6 +22,7 @@ call (the MOOLIB_AMD_* switches may change between two forwards):
 | stem, eager | all else | `.to(dtype).mul_(1/255)`, channels_last on CUDA, then section 0 |
 | section, fused | `fused_bias.available` | bias-free conv, pool, blocks through `forward_fused` with the conv bias pending |
 | section, plain | otherwise | `nn.Conv2d`, pool, blocks as plain modules |
+| section after its conv | `fused_actor_sections=True`, no grad, `fused_bias.available` and `conv3x3.actor_section_available` (MFMA blocks, two pooled images fit LDS, not NO_ACTOR_SECTION) | `conv3x3.actor_section`: pool and both blocks in one launch with the image resident in LDS, the same values as the rows below; the trunk's trailing relu rides in the last section's launch |
 | block in `forward_fused` | no grad and `conv3x3.runs_on_mfma` | two fused MFMA conv launches |
 | block in `forward_fused` | otherwise | `bias_relu`/relu, conv, `bias_relu`, conv, `bias_add2` |
 | core input | `fused_core_input=True`, the fused-scan branch is taken and `lstm_ops.core_input_available` | `lstm_ops.core_input_projection` on `relu(fc(x))`, reward, prev_action and the core's own `weight_ih_l0` and biases: no one_hot, clamp, cat or `F.linear` |
@@ -107,34 +108,46 @@ class ConvSection(nn.Module):
         self.res0 = ResidualBlock(out_ch)
         self.res1 = ResidualBlock(out_ch)
 
-    def forward(self, x):
+    def forward(self, x, actor_fused=False, relu_out=False):
         if fused_bias.available(x, self.conv.out_channels):
             # bias-free conv; per-channel bias commutes with the per-channel
             # spatial max, so it rides into res0 as a pending bias.
-            return self.after_conv(_conv3(x, self.conv), self.conv.bias)
-        return self.after_conv(self.conv(x), None)
+            return self.after_conv(_conv3(x, self.conv), self.conv.bias, actor_fused, relu_out)
+        return self.after_conv(self.conv(x), None, actor_fused, relu_out)
 
-    def after_conv(self, u, pending_bias):
-        """Everything after the section conv: pool, res0, res1. `u` is the
-        conv's output, short of `pending_bias` (a bias the conv left out)
-        unless that is None."""
+    def after_conv(self, u, pending_bias, actor_fused=False, relu_out=False):
+        """Everything after the section conv: pool, res0, res1, and a relu
+        if `relu_out`. `u` is the conv's output, short of `pending_bias` (a
+        bias the conv left out) unless that is None. `actor_fused` asks for
+        the one-launch route where it applies."""
+        if (
+            actor_fused
+            and not torch.is_grad_enabled()
+            and fused_bias.available(u)
+            and c3.actor_section_available(u, self.conv.out_channels)
+        ):
+            return c3.actor_section(u, pending_bias, self.res0, self.res1, relu_out)
         u = maxpool3x3s2(u)
         if fused_bias.available(u):
             u = self.res0.forward_fused(u, pending_bias)
-            return self.res1.forward_fused(u)
-        assert pending_bias is None
-        return self.res1(self.res0(u))
+            u = self.res1.forward_fused(u)
+        else:
+            assert pending_bias is None
+            u = self.res1(self.res0(u))
+        return F.relu(u) if relu_out else u
 
 
 class AtariNet(nn.Module):
     def __init__(self, num_actions=18, input_channels=4, use_lstm=False, lstm_size=256,
-                 fused_core_input=False, fused_core_recurrent=False):
+                 fused_core_input=False, fused_core_recurrent=False,
+                 fused_actor_sections=False):
         super().__init__()
         self.num_actions = num_actions
         self.use_lstm = use_lstm
         # opt-in routes, no module or parameter of their own (see the route table)
         self.fused_core_input = fused_core_input
         self.fused_core_recurrent = fused_core_recurrent
+        self.fused_actor_sections = fused_actor_sections
 
         chans = [16, 32, 32]
         sections = []
@@ -172,6 +185,7 @@ class AtariNet(nn.Module):
     def stem(self, x):
         """Frames [N, C, 84, 84] (uint8 0..255) through section 0."""
         sec0 = self.sections[0]
+        fused = self.fused_actor_sections
         kernels = None
         if x.is_cuda and x.dtype == torch.uint8 and c3.bf16_compute(self.fc.weight):
             kernels = c3.kernels()
@@ -186,7 +200,7 @@ class AtariNet(nn.Module):
             # kernel + a bias-sum — the first layer never touches MIOpen in
             # either direction.
             x = c3.conv1_u8_autograd(x, sec0.conv, 1.0 / 255.0)
-            return sec0.after_conv(x, None)
+            return sec0.after_conv(x, None, fused)
         if kernels is not None and not os.environ.get("MOOLIB_AMD_NO_FRAMES_KERNEL"):
             x = kernels.frames_u8_to_bf16_nhwc(x, 1.0 / 255.0)
         else:
@@ -198,16 +212,17 @@ class AtariNet(nn.Module):
                 # CPU/NCHW path — a self-consistent permutation of learned
                 # features.)
                 x = x.contiguous(memory_format=torch.channels_last)
-        return sec0(x)
+        return sec0(x, fused)
 
     def forward(self, inputs, core_state=None):
         x = inputs["state"]
         reward = inputs["reward"]
         T, B = x.shape[:2]
         x = self.stem(x.flatten(0, 1))
-        for s in self.sections[1:]:
-            x = s(x)
-        x = F.relu(x)
+        for s in self.sections[1:-1]:
+            x = s(x, self.fused_actor_sections)
+        # the trunk's trailing relu is the last section's to apply
+        x = self.sections[-1](x, self.fused_actor_sections, relu_out=True)
         x = x.reshape(T * B, -1)
         x = F.relu(self.fc(x))
 
@@ -301,9 +316,11 @@ class AtariNet(nn.Module):
 
 
 def create_model(num_actions=18, use_lstm=False, device="cpu", lstm_size=256,
-                 fused_core_input=False, fused_core_recurrent=False):
+                 fused_core_input=False, fused_core_recurrent=False,
+                 fused_actor_sections=False):
     model = AtariNet(num_actions=num_actions, use_lstm=use_lstm, lstm_size=lstm_size,
                      fused_core_input=fused_core_input,
-                     fused_core_recurrent=fused_core_recurrent)
+                     fused_core_recurrent=fused_core_recurrent,
+                     fused_actor_sections=fused_actor_sections)
     model.to(device)
     return model

@@ -9,7 +9,9 @@ kernel launches on the actor. The learner uses `conv3x3_autograd`
 wrw by default, our wgrad3x3 kernel opt-in); `conv1_u8_autograd` is the
 uint8 first layer of both. `runs_on_mfma` is the one place that decides
 whether a conv takes the kernel, `packed` the one cache of packed weights
-(kinds in PACKERS), refreshed by `repack`.
+(kinds in PACKERS), refreshed by `repack`. `actor_section` wraps
+hip/actor_section.hip.inc: pool and both residual blocks of a trunk section
+in one launch on the same packs, for the actor (docs/ACTOR_SECTION.md).
 """
 import os
 
@@ -294,4 +296,32 @@ def conv3x3(x, w_packed, k, relu_in=False, bias_in=None, epi=EPI_NONE,
         None if res is None else to_bf(res).contiguous(memory_format=torch.channels_last),
         to_bf(bias2),
         rt,
+    )
+
+
+def actor_section_available(u, K):
+    """Can `actor_section` take everything after a section conv whose output
+    is `u` [N, K, H, W]? The blocks' convs must be MFMA convs and two
+    zero-haloed pooled images must fit the workgroup's LDS.
+    MOOLIB_AMD_NO_ACTOR_SECTION=1 switches the route off."""
+    if os.environ.get("MOOLIB_AMD_NO_ACTOR_SECTION") or not runs_on_mfma(u, K, K):
+        return False
+    oh, ow = (u.size(2) + 1) // 2, (u.size(3) + 1) // 2
+    return 2 * (oh + 2) * (ow + 2) * K * 2 <= _k().ACTOR_SECTION_LDS_MAX
+
+
+def actor_section(u, pending_bias, res0, res1, relu_out=False):
+    """maxpool3x3s2(u), then res0.forward_fused(., pending_bias) and
+    res1.forward_fused(.) as the no-grad MFMA route computes them, bit for
+    bit, then relu if `relu_out`: one launch, the pooled image resident in
+    LDS. Reads the persistent "fwd" packs, so a captured graph sees what
+    repack() refreshes."""
+    convs = (res0.conv0, res0.conv1, res1.conv0, res1.conv1)
+    to_bf = lambda t: None if t is None else t.detach().to(torch.bfloat16)
+    return _k().actor_section_nhwc(
+        u.to(torch.bfloat16).contiguous(memory_format=torch.channels_last),
+        to_bf(pending_bias),
+        [packed(c) for c in convs],
+        [to_bf(c.bias) for c in convs],
+        relu_out,
     )
