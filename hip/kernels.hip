@@ -413,6 +413,7 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 #include "lstm.hip.inc"
 #include "lstm_wide.hip.inc"
 #include "lstm_input.hip.inc"
+#include "fc.hip.inc"
 #include "lstm_whh.hip.inc"
 #include "r2d2.hip.inc"
 
@@ -775,6 +776,160 @@ std::vector<at::Tensor> lstm_input_bwd(at::Tensor dXg, at::Tensor feat, at::Tens
                      dim3(lstm_input::kThreads), 0, stream, ws.data_ptr<float>(),
                      dW.data_ptr<float>(), db.data_ptr<float>(), slabs, s.N, s.K, nCT * 16);
   return {dFeat, dW, db};
+}
+
+// ---- fused trunk FC (fc.hip.inc)
+
+struct FcShape {
+  int M, P;
+};
+
+// Everything the kernels index by: x [M,32,Hh,Ww] bf16, channels_last-dense
+// and 16-byte aligned; W [256, 32*Hh*Ww] fp32 or bf16, contiguous, on x's device.
+static FcShape checkFc(const at::Tensor& x, const at::Tensor& W, const char* who) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kBFloat16, who,
+              ": x must be a [M, 32, Hh, Ww] bf16 CUDA tensor, got ", x.scalar_type(), " ",
+              x.sizes());
+  TORCH_CHECK(x.size(1) == fc::kC, who, ": x must have ", fc::kC, " channels, got ", x.size(1));
+  const int64_t P = x.size(2) * x.size(3);
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= (1 << 24) && P >= 1 && P <= (1 << 16), who,
+              ": M must be 1 to 2^24 rows and Hh*Ww 1 to 2^16 pixels");
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              who, ": x must be channels_last-dense and 16-byte aligned");
+  TORCH_CHECK(W.is_cuda() && W.device() == x.device() && W.dim() == 2 &&
+                  (W.scalar_type() == at::kFloat || W.scalar_type() == at::kBFloat16),
+              who, ": weight must be a [256, 32*Hh*Ww] fp32 or bf16 tensor on x's device");
+  TORCH_CHECK(W.size(0) == fc::kN && W.size(1) == fc::kC * P, who, ": weight must be [", fc::kN,
+              ", ", fc::kC * P, "], got ", W.sizes());
+  TORCH_CHECK(W.is_contiguous(), who, ": weight must be contiguous");
+  return {(int)x.size(0), (int)P};
+}
+
+static int fcRowTile(int M) { return M < 1024 ? 2 : 4; }  // BM / 16, see fc.hip.inc
+
+// The forward's split of the pixel axis: S slabs of pp pixels, from (M, P)
+// alone, or from splitK >= 1 (clamped to P). No slab is empty.
+static void fcSplit(int M, int P, int64_t splitK, int& S, int& pp) {
+  if (splitK >= 1) {
+    const int s = (int)std::min<int64_t>(splitK, P);
+    pp = (P + s - 1) / s;
+  } else {
+    const int BM = fcRowTile(M) * 16;
+    const int chunks = (P + fc::kPC - 1) / fc::kPC;
+    const int base = (M + BM - 1) / BM * (fc::kN / fc::kBN);
+    const int want = std::min(std::min(std::max((256 + base - 1) / base, 1), 16), chunks);
+    pp = (chunks + want - 1) / want * fc::kPC;
+  }
+  S = (P + pp - 1) / pp;
+}
+
+template <typename WT>
+static void fcFwdLaunch(const FcShape& s, const at::Tensor& x, const at::Tensor& W,
+                        const at::Tensor& bias, int biasKind, at::Tensor& feat, float* ws, int S,
+                        int pp, bool reluIn) {
+  using bf16 = lstm::bf16;
+  auto stream = c10::hip::getCurrentHIPStream();
+  auto launch = [&](auto rt) {
+    constexpr int RT = decltype(rt)::value;
+    dim3 grid((s.M + RT * 16 - 1) / (RT * 16), fc::kN / fc::kBN, S);
+    hipLaunchKernelGGL((fc::fwd_kernel<WT, RT>), grid, dim3(fc::kThreads), 0, stream,
+                       reinterpret_cast<const bf16*>(x.data_ptr()),
+                       reinterpret_cast<const WT*>(W.data_ptr()), bias.data_ptr(), biasKind,
+                       reinterpret_cast<bf16*>(feat.data_ptr()), ws, s.M, s.P, pp, (int)reluIn);
+  };
+  if (fcRowTile(s.M) == 2)
+    launch(std::integral_constant<int, 2>());
+  else
+    launch(std::integral_constant<int, 4>());
+}
+
+at::Tensor trunk_fc_fwd(at::Tensor x, at::Tensor W, at::Tensor bias, bool reluIn,
+                        int64_t splitK) {
+  const char* who = "trunk fc fwd";
+  FcShape s = checkFc(x, W, who);
+  const int biasKind = lstmInputRealKind(bias, who, "bias");
+  checkLstmArg(bias, x, bias.scalar_type(), {fc::kN}, who, "bias");
+  int S, pp;
+  fcSplit(s.M, s.P, splitK, S, pp);
+  auto feat = at::empty({s.M, fc::kN}, x.options());
+  at::Tensor ws;
+  if (S > 1) ws = at::empty({S, s.M, fc::kN}, x.options().dtype(at::kFloat));
+  float* wsp = S > 1 ? ws.data_ptr<float>() : nullptr;
+  if (W.scalar_type() == at::kFloat)
+    fcFwdLaunch<float>(s, x, W, bias, biasKind, feat, wsp, S, pp, reluIn);
+  else
+    fcFwdLaunch<lstm::bf16>(s, x, W, bias, biasKind, feat, wsp, S, pp, reluIn);
+  if (S > 1) {
+    const int64_t threads = (int64_t)s.M * fc::kN / 4;
+    hipLaunchKernelGGL(fc::fwd_reduce_kernel,
+                       dim3((threads + fc::kThreads - 1) / fc::kThreads), dim3(fc::kThreads), 0,
+                       c10::hip::getCurrentHIPStream(), wsp, bias.data_ptr(), biasKind,
+                       reinterpret_cast<lstm::bf16*>(feat.data_ptr()), s.M, S);
+  }
+  return feat;
+}
+
+template <typename WT>
+static void fcDgradLaunch(const FcShape& s, const at::Tensor& dY, const at::Tensor& feat,
+                          const at::Tensor& W, const at::Tensor& x, at::Tensor& dx, bool reluIn) {
+  using bf16 = lstm::bf16;
+  auto stream = c10::hip::getCurrentHIPStream();
+  auto launch = [&](auto rt) {
+    constexpr int RT = decltype(rt)::value;
+    dim3 grid((s.M + RT * 16 - 1) / (RT * 16), (s.P + fc::kPC - 1) / fc::kPC);
+    hipLaunchKernelGGL((fc::dgrad_kernel<WT, RT>), grid, dim3(fc::kThreads), 0, stream,
+                       reinterpret_cast<const bf16*>(dY.data_ptr()),
+                       reinterpret_cast<const bf16*>(feat.data_ptr()),
+                       reinterpret_cast<const WT*>(W.data_ptr()),
+                       reinterpret_cast<const bf16*>(x.data_ptr()),
+                       reinterpret_cast<bf16*>(dx.data_ptr()), s.M, s.P, (int)reluIn);
+  };
+  if (fcRowTile(s.M) == 2)
+    launch(std::integral_constant<int, 2>());
+  else
+    launch(std::integral_constant<int, 4>());
+}
+
+// Returns (d_x like x, bf16 channels_last, or an undefined tensor; dW [256,
+// 32 P] fp32 in nn.Linear's column order; db [256] fp32). `feat` is the
+// forward's output: its sign is the fc relu's mask.
+std::vector<at::Tensor> trunk_fc_bwd(at::Tensor dY, at::Tensor x, at::Tensor feat, at::Tensor W,
+                                     bool reluIn, bool needX) {
+  const char* who = "trunk fc bwd";
+  FcShape s = checkFc(x, W, who);
+  checkLstmArg(dY, x, at::kBFloat16, {s.M, fc::kN}, who, "dY");
+  checkLstmArg(feat, x, at::kBFloat16, {s.M, fc::kN}, who, "feat");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dY.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(feat.data_ptr()) % 16 == 0,
+              who, ": dY and feat must be 16-byte aligned");
+  using bf16 = lstm::bf16;
+  auto stream = c10::hip::getCurrentHIPStream();
+  at::Tensor dx;
+  if (needX) {
+    dx = at::empty(x.sizes(), x.options().memory_format(at::MemoryFormat::ChannelsLast));
+    if (W.scalar_type() == at::kFloat)
+      fcDgradLaunch<float>(s, dY, feat, W, x, dx, reluIn);
+    else
+      fcDgradLaunch<bf16>(s, dY, feat, W, x, dx, reluIn);
+  }
+  auto fopts = x.options().dtype(at::kFloat);
+  const int slabs = (s.M + fc::kSlab - 1) / fc::kSlab;
+  const int chunks = (s.P + fc::kPC - 1) / fc::kPC;
+  const int64_t K = (int64_t)fc::kC * s.P;
+  auto ws = at::empty({slabs, fc::kN, K}, fopts);
+  auto wsb = at::empty({slabs, fc::kN}, fopts);
+  auto dW = at::empty({fc::kN, K}, fopts);
+  auto db = at::empty({fc::kN}, fopts);
+  hipLaunchKernelGGL(fc::wgrad_kernel, dim3(fc::kN / fc::kBN, chunks, slabs), dim3(fc::kThreads),
+                     0, stream, reinterpret_cast<const bf16*>(dY.data_ptr()),
+                     reinterpret_cast<const bf16*>(feat.data_ptr()),
+                     reinterpret_cast<const bf16*>(x.data_ptr()), ws.data_ptr<float>(),
+                     wsb.data_ptr<float>(), s.M, s.P, (int)reluIn);
+  hipLaunchKernelGGL(fc::wgrad_reduce_kernel, dim3(chunks, fc::kN), dim3(fc::kThreads), 0, stream,
+                     ws.data_ptr<float>(), wsb.data_ptr<float>(), dW.data_ptr<float>(),
+                     db.data_ptr<float>(), slabs, s.P);
+  return {dx, dW, db};
 }
 
 // ---- recurrent weight gradient and W_hh pack (lstm_whh.hip.inc)
@@ -1585,6 +1740,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_input_bwd", &lstm_input_bwd,
         "fused LSTM input projection bwd: d_feat, dW_ih and the bias gradient, deterministic");
   m.attr("LSTM_INPUT_MAX_ACTIONS") = lstm_input::kMaxActions;  // widest action set served
+  m.def("trunk_fc_fwd", &trunk_fc_fwd,
+        "fused trunk FC: NHWC x -> relu(fc), W read in place, split-K MFMA (gfx950)");
+  m.def("trunk_fc_bwd", &trunk_fc_bwd,
+        "trunk FC backward: masked dgrad to NHWC, dW in nn.Linear's order and db, no atomics");
   m.def("lstm_whh_grad", &lstm_whh_grad,
         "dW_hh = dG^T @ shifted, masked H: MFMA slab partials + fixed-order reduce, no atomics");
   m.def("lstm_whh_pack", &lstm_whh_pack,

@@ -89,6 +89,11 @@ class ImpalaConfig:
     #   LDS (ops.conv3x3.actor_section), 3 graph nodes where there were 15
     #   and the same values bit for bit (docs/ACTOR_SECTION.md).
     #   MOOLIB_AMD_NO_ACTOR_SECTION=1 switches it off.
+    fused_trunk_fc: bool = False  # the trunk's FC layer as one op on the
+    #   channels_last features and fc's own weight (ops.fc.trunk_fc: split-K
+    #   MFMA forward, masked dgrad, weight gradient in nn.Linear's order), in
+    #   the actor's and the learner's forward alike.
+    #   MOOLIB_AMD_FUSED_TRUNK_FC=1 switches it on.
     graph_learner: bool = False  # hipGraph-capture the learner fwd+bwd.
     #   OFF by default: replays of the captured learner (autograd backward
     #   incl. MIOpen bwd-weight convs) intermittently fault on ROCm 7.0
@@ -264,6 +269,8 @@ class ImpalaPeer:
             cfg.fused_optimizer = True
         if os.environ.get("MOOLIB_AMD_FUSED_SAMPLING", "0") == "1":
             cfg.fused_sampling = True
+        if os.environ.get("MOOLIB_AMD_FUSED_TRUNK_FC", "0") == "1":
+            cfg.fused_trunk_fc = True
         if cfg.fused_optimizer:
             # optim.FlatAdam, built by _build_fused_optimizer once the flat
             # buffers exist
@@ -367,6 +374,9 @@ class ImpalaPeer:
         if hasattr(self.fwd_model, "fused_actor_sections"):
             # a route of the no-grad forward only: the learner's is untouched
             self.fwd_model.fused_actor_sections = cfg.fused_actor_sections
+        for m in {id(m): m for m in (self.model, self.fwd_model)}.values():
+            if hasattr(m, "fused_trunk_fc"):
+                m.fused_trunk_fc = cfg.fused_trunk_fc
         if cfg.fused_optimizer:
             self._build_fused_optimizer()
         self.env_states = [

@@ -25,6 +25,8 @@ call (the MOOLIB_AMD_* switches may change between two forwards):
 | section after its conv | `fused_actor_sections=True`, no grad, `fused_bias.available` and `conv3x3.actor_section_available` (MFMA blocks, two pooled images fit LDS, not NO_ACTOR_SECTION) | `conv3x3.actor_section`: pool and both blocks in one launch with the image resident in LDS, the same values as the rows below; the trunk's trailing relu rides in the last section's launch |
 | block in `forward_fused` | no grad and `conv3x3.runs_on_mfma` | two fused MFMA conv launches |
 | block in `forward_fused` | otherwise | `bias_relu`/relu, conv, `bias_relu`, conv, `bias_add2` |
+| trunk FC | `fused_trunk_fc=True`, the tensor entering the last section is CUDA with bf16 compute and `fc_ops.trunk_fc_available` | the last section runs with `relu_out=False`; `fc_ops.trunk_fc(x, fc.weight, fc.bias, relu_in=True)` (hip/fc.hip.inc) is the trunk's trailing relu, the flatten, `fc` and its relu on the channels_last tensor and `fc`'s own weight: no layout copy, weight cast or vendor GEMM, in grad and no-grad mode alike |
+| trunk FC | otherwise | the last section applies the relu; `reshape` (a copy to NCHW order), `self.fc`, `F.relu` |
 | core input | `fused_core_input=True`, the fused-scan branch is taken and `lstm_ops.core_input_available` | `lstm_ops.core_input_projection` on `relu(fc(x))`, reward, prev_action and the core's own `weight_ih_l0` and biases: no one_hot, clamp, cat or `F.linear` |
 | core input | otherwise | one_hot, clamp, cat; on the fused-scan branch `F.linear` over all T |
 | core recurrent weight | `fused_core_recurrent=True` and the fused-scan branch is taken | `fused_lstm_scan(..., native_whh=True)`: one pack launch for `weight_hh_l0`, `lstm_ops.recurrent_weight_grad` for its gradient |
@@ -41,6 +43,7 @@ from torch import nn
 
 from moolib_amd.ops import act as act_ops
 from moolib_amd.ops import conv3x3 as c3
+from moolib_amd.ops import fc as fc_ops
 from moolib_amd.ops import fused_bias
 from moolib_amd.ops import lstm as lstm_ops
 from moolib_amd.ops.fused_bias import bias_add2, bias_relu
@@ -140,7 +143,7 @@ class ConvSection(nn.Module):
 class AtariNet(nn.Module):
     def __init__(self, num_actions=18, input_channels=4, use_lstm=False, lstm_size=256,
                  fused_core_input=False, fused_core_recurrent=False,
-                 fused_actor_sections=False):
+                 fused_actor_sections=False, fused_trunk_fc=False):
         super().__init__()
         self.num_actions = num_actions
         self.use_lstm = use_lstm
@@ -148,6 +151,7 @@ class AtariNet(nn.Module):
         self.fused_core_input = fused_core_input
         self.fused_core_recurrent = fused_core_recurrent
         self.fused_actor_sections = fused_actor_sections
+        self.fused_trunk_fc = fused_trunk_fc
 
         chans = [16, 32, 32]
         sections = []
@@ -221,10 +225,21 @@ class AtariNet(nn.Module):
         x = self.stem(x.flatten(0, 1))
         for s in self.sections[1:-1]:
             x = s(x, self.fused_actor_sections)
-        # the trunk's trailing relu is the last section's to apply
-        x = self.sections[-1](x, self.fused_actor_sections, relu_out=True)
-        x = x.reshape(T * B, -1)
-        x = F.relu(self.fc(x))
+        if (
+            self.fused_trunk_fc
+            and x.is_cuda
+            and c3.bf16_compute(x)
+            and fc_ops.trunk_fc_available(self.sections[-1].conv.out_channels, x.device)
+        ):
+            # the trunk's trailing relu, the flatten, fc and its relu in one op
+            # on the channels_last tensor and fc's own weight
+            x = self.sections[-1](x, self.fused_actor_sections, relu_out=False)
+            x = fc_ops.trunk_fc(x, self.fc.weight, self.fc.bias, relu_in=True)
+        else:
+            # the trunk's trailing relu is the last section's to apply
+            x = self.sections[-1](x, self.fused_actor_sections, relu_out=True)
+            x = x.reshape(T * B, -1)
+            x = F.relu(self.fc(x))
 
         fused_scan = (
             self.use_lstm
@@ -317,10 +332,11 @@ class AtariNet(nn.Module):
 
 def create_model(num_actions=18, use_lstm=False, device="cpu", lstm_size=256,
                  fused_core_input=False, fused_core_recurrent=False,
-                 fused_actor_sections=False):
+                 fused_actor_sections=False, fused_trunk_fc=False):
     model = AtariNet(num_actions=num_actions, use_lstm=use_lstm, lstm_size=lstm_size,
                      fused_core_input=fused_core_input,
                      fused_core_recurrent=fused_core_recurrent,
-                     fused_actor_sections=fused_actor_sections)
+                     fused_actor_sections=fused_actor_sections,
+                     fused_trunk_fc=fused_trunk_fc)
     model.to(device)
     return model
