@@ -334,13 +334,15 @@ def lstm_exact(d):
             "dc0": c0.grad, "dW": w.grad}
 
 
-def lstm_emul(d, rounding=True):
+def lstm_emul(d, rounding=True, round_g=True):
     """R_emul: the same recurrence and its hand-written backward in fp64 with
     the kernel's bf16 rounding points (hip/lstm.hip.inc, ops/lstm.py):
     h after masking and after each step, G = X + hW before the gates, the
     saved gates, dG before the dG.W GEMM and in dW, and dh0.
-    rounding=False switches every rounding point off."""
+    rounding=False switches every rounding point off; round_g=False only the
+    one of G, which hip/lstm_wide.hip.inc (128 and 512 units) keeps in fp32."""
     r = bf16_round if rounding else (lambda t: t)
+    rg = r if round_g else (lambda t: t)
     X, h0, c0, w, nd = d["X"], d["h0"], d["c0"], d["w"], d["nd"]
     T, B, _ = X.shape
     h, c = h0, c0
@@ -349,7 +351,7 @@ def lstm_emul(d, rounding=True):
         m = nd[t].unsqueeze(-1)
         h, c = r(h * m), c * m
         hm.append(h)
-        G = r(X[t] + h @ w.t())
+        G = rg(X[t] + h @ w.t())
         i, f, g, o = G.chunk(4, dim=-1)
         i, f, g, o = torch.sigmoid(i), torch.sigmoid(f), torch.tanh(g), torch.sigmoid(o)
         c = f * c + i * g

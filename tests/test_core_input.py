@@ -108,6 +108,8 @@ def test_backward_is_deterministic():
 @gpu
 @requires_gpu
 def test_model_route(monkeypatch):
+    # a route check; what the route computes (outputs, state, every gradient)
+    # is held to float64 in tests/test_core_composed.py
     from moolib_amd.models.atari import AtariNet
     from moolib_amd.ops import lstm as lstm_ops
 

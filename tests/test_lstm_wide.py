@@ -89,7 +89,9 @@ def test_forward_only_equals_saving_forward(hidden, T, B):
 @gpu
 @requires_gpu
 def test_model_route_512(monkeypatch):
-    """AtariNet with a 512-unit core: fused scan vs the per-step nn.LSTM loop."""
+    """AtariNet with a 512-unit core: fused scan vs the per-step nn.LSTM loop.
+    (A route check; the values of this route, state and gradients included,
+    are held to float64 in tests/test_core_composed.py.)"""
     from moolib_amd.models.atari import AtariNet
 
     torch.manual_seed(7)

@@ -200,28 +200,71 @@ class _LstmEmulFn(torch.autograd.Function):
     kernel's rounding points) as one autograd node."""
 
     @staticmethod
-    def forward(ctx, X, h0, c0, w, nd, rounding_on):
+    def forward(ctx, X, h0, c0, w, nd, rounding_on, round_g, dw_unshifted):
         z = torch.zeros
         d = {"X": X, "h0": h0, "c0": c0, "w": w, "nd": nd,
              "gH": z(X.shape[0], X.shape[1], h0.shape[1], dtype=F64),
              "ghT": z(h0.shape, dtype=F64), "gcT": z(h0.shape, dtype=F64)}
-        out = R.lstm_emul(d, rounding_on)
-        ctx.d, ctx.rounding_on = d, rounding_on
+        out = R.lstm_emul(d, rounding_on, round_g)
+        ctx.d, ctx.flags, ctx.H = d, (rounding_on, round_g), out["H"]
+        ctx.dw_unshifted = dw_unshifted
         return out["H"], out["hT"], out["cT"]
 
     @staticmethod
     def backward(ctx, gH, ghT, gcT):
-        out = R.lstm_emul(dict(ctx.d, gH=gH, ghT=ghT, gcT=gcT), ctx.rounding_on)
-        return out["dX"], out["dh0"], out["dc0"], out["dW"], None, None
+        out = R.lstm_emul(dict(ctx.d, gH=gH, ghT=ghT, gcT=gcT), *ctx.flags)
+        dW = out["dW"]
+        if ctx.dw_unshifted:  # the mutation: dG[t]^T @ H[t] where H[t-1] belongs
+            dW = torch.einsum("tbg,tbh->gh", out["dX"], ctx.H)
+        return out["dX"], out["dh0"], out["dc0"], dW, None, None, None, None
 
 
-def lstm(X, h0, c0, w, nd, force_emul=False):
+def lstm(X, h0, c0, w, nd, force_emul=False, round_g=True, dw_unshifted=False):
     """lstm_emul when the activation Qs are on, else the plain recurrence;
     `force_emul` runs lstm_emul with its rounding off instead (the two must
-    then agree)."""
-    if _state["act"] or force_emul:
-        return _LstmEmulFn.apply(X, h0, c0, w, nd, _state["act"])
+    then agree). `round_g=False` leaves G = X + hW unrounded, as the 128 / 512
+    kernels do. `dw_unshifted` is a mutation of lstm_emul's backward."""
+    if _state["act"] or force_emul or dw_unshifted:
+        return _LstmEmulFn.apply(X, h0, c0, w, nd, _state["act"], round_g, dw_unshifted)
     return lstm_plain(X, h0, c0, w, nd)
+
+
+def fc_relu(flat, w, b, fused=False):
+    """relu(fc(flat)) on `flat`, the relu'd trunk output. Default route: the
+    bf16 GEMM of `linear`, then relu (a selection, no rounding). `fused`
+    (ops/fc.py::trunk_fc, hip/fc.hip.inc): fp32 sum, bias and relu, one
+    rounding; d_x rounded once; dW and db stay fp32 sums (no Q of their own).
+    The values agree: rounding commutes with relu, in both directions."""
+    if fused:
+        return Q(torch.relu(Q(flat, fwd=False) @ w.t() + b))
+    return torch.relu(linear(flat, w, b))
+
+
+def core_input_proj(feat, reward, action, w, b_ih, b_hh, fused=False, mutate=()):
+    """The LSTM's input projection Xg [M,4H] from feat [M,F], reward [M],
+    prev_action [M], weight_ih_l0 [4H, F+1+A] (columns: features, reward,
+    actions) and both biases.
+
+    Default route (models/atari.py: clamp, one_hot, cat, F.linear): the clamped
+    reward is cast to bf16, the bias sum is rounded, the GEMM is bf16 (output,
+    dx, dW, db all rounded). `fused` (ops/lstm.py::core_input_projection,
+    hip/lstm_input.hip.inc): reward clamped in fp32 and not rounded, biases
+    added in fp32, one rounding of Xg; d_feat rounded once; dW and db are fp32
+    sums. Mutations: reward_unclamped, action_shifted."""
+    M, F_ = feat.shape
+    A = w.shape[1] - F_ - 1
+    r = reward.reshape(M).to(F64)
+    if "reward_unclamped" not in mutate:
+        r = r.clamp(-1, 1)
+    if not fused:
+        r = Q(r)
+    extra = torch.zeros(M, 1 + A, dtype=F64)
+    extra[:, 0] = r
+    first = 0 if "action_shifted" in mutate else 1
+    extra[torch.arange(M), first + action.reshape(M).long()] += 1.0
+    if fused:
+        return Q(Q(feat, fwd=False) @ w[:, :F_].t() + extra @ w[:, F_:].t() + b_ih + b_hh)
+    return linear(torch.cat([feat, extra], dim=-1), w, b_ih + b_hh)
 
 
 # ------------------------------------------------------------------ the net
@@ -267,57 +310,119 @@ def trunk(frames_u8, p, mode, wgrad, mutate=()):
     return x.reshape(x.shape[0], -1)
 
 
+def trunk_graph(params, frames_u8, mode="a", wgrad="kernel", mutate=()):
+    """The trunk's forward, kept with its autograd graph, so that several
+    networks that share frames and section parameters (the core cases of
+    three widths) pay for it once: hand it to `atari_ref(trunk_cache=...)`.
+    Built under the `rounding` context it is meant for."""
+    leaves = {k: params[k].detach().to(F64).clone().requires_grad_() for k in SECTION_PARAMS}
+    return {"leaves": leaves, "flat": trunk(frames_u8, leaves, mode, wgrad, mutate),
+            "key": (mode, wgrad, tuple(mutate), dict(_state))}
+
+
+# mutations of the core's wiring that `atari_ref(mutate=...)` knows
+CORE_MUTATIONS = ("reward_unclamped", "action_shifted", "no_bias_hh", "bias_hh_no_grad",
+                  "dw_hh_unshifted", "h0_unmasked", "state_from_t_minus_2", "c0_bf16",
+                  "whh_i_f_swapped")
+
+
 def atari_ref(params, inputs, core_state=None, mode="a", wgrad="kernel", grads=None,
-              mutate=()):
+              mutate=(), trunk_fc=False, core_input=False, core_recurrent=False,
+              trunk_cache=None):
     """Forward and backward of AtariNet in fp64.
 
     params: state_dict names -> tensors (any float dtype). inputs: state u8
     [T,B,4,84,84], reward, prev_action, done. core_state: (h0, c0) as
-    [1,B,256] for the LSTM variant (recognised by `core.weight_hh_l0`).
+    [1,B,H] for the LSTM variant (recognised by `core.weight_hh_l0`, whose
+    second extent is the hidden size H; 128 and 512 keep G = X + hW in fp32).
+    trunk_fc, core_input, core_recurrent: the opt-in routes of the same name
+    (`fused_*` in AtariNet). They move rounding points only: with every Q off
+    the result does not depend on them. `core_recurrent` moves none (dW_hh is
+    an fp32 sum of bf16 products on either route, cast by autograd in (a)).
     grads: {"trunk": G} backpropagates G from the flattened trunk output
     alone; {"policy_logits": Gp, "baseline": Gb} backpropagates
-    (policy_logits*Gp).sum() + (baseline*Gb).sum(). Returns a dict with
-    `trunk`, `policy_logits`, `baseline`, `hT`, `cT` and `grads` (name -> fp64
-    gradient, for every parameter that received one)."""
-    leaves = {k: v.detach().to(F64).clone().requires_grad_() for k, v in params.items()}
+    (policy_logits*Gp).sum() + (baseline*Gb).sum(), plus (hT*ghT).sum() +
+    (cT*gcT).sum() of the returned core state when "hT" and "cT" are given.
+    Returns a dict with `trunk`, `policy_logits`, `baseline`, `hT`, `cT`,
+    `dh0`, `dc0` and `grads` (name -> fp64 gradient, for every parameter that
+    received one)."""
     x = inputs["state"]
     T, B = x.shape[:2]
-    flat = trunk(x.flatten(0, 1), {k: leaves[k] for k in SECTION_PARAMS}, mode, wgrad, mutate)
-    out = {"trunk": flat.detach()}
-    if grads is not None and "trunk" in grads:
-        flat.backward(grads["trunk"].to(F64))
+    if trunk_cache is None:
+        trunk_cache = trunk_graph(params, x.flatten(0, 1), mode, wgrad, mutate)
+        retain = False
     else:
+        assert trunk_cache["key"] == (mode, wgrad, tuple(m for m in mutate
+                                                         if m not in CORE_MUTATIONS), dict(_state))
+        retain = True
+    leaves = {k: v.detach().to(F64).clone().requires_grad_() for k, v in params.items()
+              if k not in SECTION_PARAMS}
+    leaves.update(trunk_cache["leaves"])
+    for k in SECTION_PARAMS:
+        leaves[k].grad = None
+    flat_full = trunk_cache["flat"]
+    out = {"trunk": flat_full.detach()}
+    if grads is not None and "trunk" in grads:
+        flat_full.backward(grads["trunk"].to(F64), retain_graph=retain)
+    else:
+        flat = flat_full.detach().requires_grad_()  # the head's leaf; the trunk follows below
         top_rounds = mode == "a"
         p = {k: Q(v, "param", fwd=k not in ("core.bias_ih_l0", "core.bias_hh_l0"), bwd=top_rounds)
              for k, v in leaves.items() if k not in SECTION_PARAMS}
-        h = torch.relu(linear(flat, p["fc.weight"], p["fc.bias"]))
+        h = fc_relu(flat, p["fc.weight"], p["fc.bias"], trunk_fc)
         A = p["policy.weight"].shape[0]
-        onehot = torch.nn.functional.one_hot(inputs["prev_action"].reshape(T * B).long(), A)
-        reward = Q(inputs["reward"].reshape(T * B, 1).to(F64).clamp(-1, 1))
-        core = torch.cat([h, reward, onehot.to(F64)], dim=-1)
+        reward, action = inputs["reward"].reshape(T * B), inputs["prev_action"].reshape(T * B)
+        loss = 0.0
         if "core.weight_hh_l0" in p:
-            # bias_ih + bias_hh is formed in the parameters' dtype, then bf16
-            Xg = linear(core, p["core.weight_ih_l0"], p["core.bias_ih_l0"] + p["core.bias_hh_l0"])
+            w_hh = p["core.weight_hh_l0"]
+            Hd = w_hh.shape[1]
+            assert tuple(core_state[0].shape) == (1, B, Hd) == tuple(core_state[1].shape)
+            b_ih, b_hh = p["core.bias_ih_l0"], p["core.bias_hh_l0"]
+            if "no_bias_hh" in mutate:
+                b_hh = b_hh * 0
+            if "bias_hh_no_grad" in mutate:
+                b_hh = b_hh.detach() + b_hh * 0
+            Xg = core_input_proj(h, reward, action, p["core.weight_ih_l0"], b_ih, b_hh,
+                                 core_input, mutate).view(T, B, -1)
             nd = (~inputs["done"].bool()).to(F64)
-            h0 = Q(core_state[0][0].to(F64))
-            c0 = core_state[1][0].float().to(F64)
-            H, hT, cT = lstm(Xg.view(T, B, -1), h0, c0, p["core.weight_hh_l0"], nd)
+            if "h0_unmasked" in mutate:
+                nd = nd.clone()
+                nd[0] = 1.0
+            h0_leaf = core_state[0].detach().to(F64).clone().requires_grad_()
+            c0_leaf = core_state[1].detach().float().to(F64).clone().requires_grad_()
+            h0 = Q(h0_leaf[0])  # .to(bfloat16), and its backward
+            c0 = Q(c0_leaf[0]) if "c0_bf16" in mutate else c0_leaf[0]
+            if "whh_i_f_swapped" in mutate:
+                w_hh = torch.cat([w_hh[Hd : 2 * Hd], w_hh[:Hd], w_hh[2 * Hd :]])
+            kw = {"round_g": Hd == 256, "dw_unshifted": "dw_hh_unshifted" in mutate}
+            H, hT, cT = lstm(Xg, h0, c0, w_hh, nd, **kw)
+            if "state_from_t_minus_2" in mutate:
+                _, hT, cT = lstm(Xg[: T - 1], h0, c0, w_hh, nd[: T - 1], **kw)
             core = Q(H).flatten(0, 1)
+            hT = Q(hT)  # returned as .to(core_state's fp32): its gradient is cast to bf16
             out["hT"], out["cT"] = hT.detach(), cT.detach()
+            if grads is not None and "hT" in grads:
+                loss = (hT * grads["hT"].to(F64)).sum() + (cT * grads["cT"].to(F64)).sum()
+        else:
+            onehot = torch.nn.functional.one_hot(action.long(), A).to(F64)
+            core = torch.cat([h, Q(reward.reshape(-1, 1).to(F64).clamp(-1, 1)), onehot], dim=-1)
         pl = linear(core, p["policy.weight"], p["policy.bias"]).view(T, B, A)
         bl = linear(core, p["baseline.weight"], p["baseline.bias"]).view(T, B)
         out["policy_logits"], out["baseline"] = pl.detach(), bl.detach()
         if grads is not None:
-            ((pl * grads["policy_logits"].to(F64)).sum()
+            (loss + (pl * grads["policy_logits"].to(F64)).sum()
              + (bl * grads["baseline"].to(F64)).sum()).backward()
-    out["grads"] = {k: v.grad for k, v in leaves.items() if v.grad is not None}
+            flat_full.backward(flat.grad, retain_graph=retain)
+            if "core.weight_hh_l0" in p:
+                out["dh0"], out["dc0"] = h0_leaf.grad[0], c0_leaf.grad[0]
+    out["grads"] = {k: v.grad.clone() for k, v in leaves.items() if v.grad is not None}
     return out
 
 
-def exact(params, inputs, core_state=None, grads=None, mutate=()):
-    """R_exact: every Q off."""
+def exact(params, inputs, core_state=None, grads=None, mutate=(), **kw):
+    """R_exact: every Q off. Route flags (`kw`) are accepted and change nothing."""
     with rounding(False, False):
-        return atari_ref(params, inputs, core_state, "a", "kernel", grads, mutate)
+        return atari_ref(params, inputs, core_state, "a", "kernel", grads, mutate, **kw)
 
 
 # ------------------------------------------------------------------ inputs
@@ -387,6 +492,70 @@ def float_case(use_lstm, seed=0, T=3, B=2, A=6):
     grads = {"policy_logits": torch.randn(T, B, A, generator=g),
              "baseline": torch.randn(T, B, generator=g)}
     return params, inputs, core, grads
+
+
+# the hidden unit of the never-done row whose cell state is built to cancel
+CORE_PROBE_UNIT = 5
+CORE_PROBE_C0 = 3.0078125  # halfway between the bf16 neighbours 3.0 and 3.015625
+
+
+def core_float_case(lstm_size, A=6, T=3, B=3, seed=0):
+    """Float case for the LSTM core and its routes, built like `float_case`
+    (bf16-representable parameters, biases of scale 0.1, random u8 frames).
+    Frames, section parameters and `fc` are the same for every `lstm_size`.
+
+    * initial state: h0 bf16-representable, c0 fp32, both of scale 0.3;
+    * done: row 0 at t=0 only (the initial state must be masked away), row 1
+      at t=1, row 2 never;
+    * reward: exactly +1 and -1, one value above 1, one below -1 and, in the
+      never-done row, one inside (-1, 1) that bf16 does not hold;
+    * prev_action: 0 and A-1 occur;
+    * output gradients for policy_logits, baseline and the returned hT, cT.
+
+    One hidden unit (CORE_PROBE_UNIT) is what lets a comparison against
+    max|cT| see a single bf16 rounding of c0, which moves an element by at most
+    2^-9 of itself while the bound grants 2^-8 of the tensor's maximum: cT has
+    to be small where c0 is large. The unit's forget and cell biases are +6
+    and -6 (ih + hh), its input bias -6 and its input weight on the reward
+    column 48, so it loses 1 per step where the reward is 1/3 or more and
+    stays put (0.0025 per step) where the reward is <= 0. Row 2 alone has
+    positive rewards, and there c0 is 3 + 2^-7, a bf16 rounding tie: cT is
+    about 2^-7, and rounding c0 moves it by 2^-7."""
+    from moolib_amd.models.atari import AtariNet
+
+    assert T == 3 and B == 3 and A >= 3
+    torch.manual_seed(300 + seed)  # sections and fc are drawn before the core: shared by all widths
+    model = AtariNet(num_actions=A, use_lstm=True, lstm_size=lstm_size)
+    g = torch.Generator().manual_seed(400 + seed)
+    params = {}
+    for k, v in model.state_dict().items():
+        v = v.double()
+        if k.endswith("bias") or ".bias_" in k:
+            v = torch.randn(v.shape, generator=g, dtype=F64) * 0.1
+        params[k] = R.bf16_round(v)
+    u, Hd = CORE_PROBE_UNIT, lstm_size
+    for k in ("core.bias_ih_l0", "core.bias_hh_l0"):
+        params[k][u], params[k][Hd + u], params[k][2 * Hd + u] = -3.0, 3.0, -3.0
+    params["core.weight_ih_l0"][u, model.fc.out_features] = 48.0
+    g = torch.Generator().manual_seed(500 + seed)  # inputs: the same for every width
+    done = torch.zeros(T, B, dtype=torch.bool)
+    done[0, 0] = True
+    done[1, 1] = True
+    inputs = {
+        "state": torch.randint(0, 256, (T, B, 4, 84, 84), dtype=torch.uint8, generator=g),
+        "reward": torch.tensor([[-1.0, -0.71, 0.3337], [-2.25, 0.0, 1.0], [0.0, -0.125, 2.5]]),
+        "prev_action": torch.tensor([[0, A - 1, 2], [1, 0, A - 1], [2, 1, 0]]),
+        "done": done,
+    }
+    grads = {"policy_logits": torch.randn(T, B, A, generator=g),
+             "baseline": torch.randn(T, B, generator=g)}
+    g = torch.Generator().manual_seed(600 + seed + lstm_size)
+    h0 = R.bf16_round(torch.randn(1, B, Hd, generator=g, dtype=F64) * 0.3).float()
+    c0 = torch.randn(1, B, Hd, generator=g) * 0.3
+    c0[0, 2, u] = CORE_PROBE_C0
+    grads["hT"] = torch.randn(B, Hd, generator=g)
+    grads["cT"] = torch.randn(B, Hd, generator=g)
+    return params, inputs, (h0, c0), grads
 
 
 # ------------------------------------------------------------------ comparisons
