@@ -66,7 +66,7 @@ def _add_sequences(buf, actor_rpc, sumtree, items, priorities):
 def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_envs=32,
         seconds=20.0, ipc=False, min_replay=None, sumtree=False, fused_act=False,
         period=None, actor_priorities=False, fused_core_input=False,
-        fused_core_recurrent=False, fused_trunk_fc=False):
+        fused_core_recurrent=False, fused_trunk_fc=False, fused_heads=False):
     """Run the workload; returns a metrics dict."""
     device = device or ("cuda:0" if torch.cuda.is_available() else "cpu")
     ipc = bool(ipc and str(device).startswith("cuda"))
@@ -88,7 +88,8 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
     )
     learner = R2D2Learner(
         AtariNet(num_actions=18, use_lstm=True, fused_core_input=fused_core_input,
-                 fused_core_recurrent=fused_core_recurrent, fused_trunk_fc=fused_trunk_fc),
+                 fused_core_recurrent=fused_core_recurrent, fused_trunk_fc=fused_trunk_fc,
+                 fused_heads=fused_heads),
         R2D2Config(burn_in=burn_in, epsilon=0.05, fused_act=fused_act),
         device,
     )
@@ -219,6 +220,7 @@ def run(device=None, capacity=2048, unroll=40, burn_in=10, batch_size=16, num_en
         "fused_core_input": bool(fused_core_input),
         "fused_core_recurrent": bool(fused_core_recurrent),
         "fused_trunk_fc": bool(fused_trunk_fc),
+        "fused_heads": bool(fused_heads),
         "device": str(device),
     }
     if builder is not None:
@@ -254,11 +256,14 @@ def main():
                     help="weight_hh pack and its gradient on kernels, not torch ops")
     ap.add_argument("--fused-trunk-fc", action="store_true",
                     help="the trunk's FC layer as one op on the channels_last features")
+    ap.add_argument("--fused-heads", action="store_true",
+                    help="the Q heads as one op on their own weights, fp32 outputs")
     a = ap.parse_args()
     m = run(a.device, a.capacity, a.unroll, a.burn_in, a.batch_size, a.num_envs, a.seconds,
             a.ipc, sumtree=a.sumtree, fused_act=a.fused_act, period=a.period,
             actor_priorities=a.actor_priorities, fused_core_input=a.fused_core_input,
-            fused_core_recurrent=a.fused_core_recurrent, fused_trunk_fc=a.fused_trunk_fc)
+            fused_core_recurrent=a.fused_core_recurrent, fused_trunk_fc=a.fused_trunk_fc,
+            fused_heads=a.fused_heads)
     print(
         "r2d2: %.1fs, %d frames acted (%.0f/s), buffer %d/%d seqs, %d learner steps, "
         "%d sequences sampled (%.0f/s), mean |TD| %.4f, loss %.4f"

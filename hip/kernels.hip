@@ -413,6 +413,7 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 #include "lstm.hip.inc"
 #include "lstm_wide.hip.inc"
 #include "lstm_input.hip.inc"
+#include "heads.hip.inc"
 #include "fc.hip.inc"
 #include "lstm_whh.hip.inc"
 #include "r2d2.hip.inc"
@@ -776,6 +777,180 @@ std::vector<at::Tensor> lstm_input_bwd(at::Tensor dXg, at::Tensor feat, at::Tens
                      dim3(lstm_input::kThreads), 0, stream, ws.data_ptr<float>(),
                      dW.data_ptr<float>(), db.data_ptr<float>(), slabs, s.N, s.K, nCT * 16);
   return {dFeat, dW, db};
+}
+
+// ---- fused policy and baseline heads (heads.hip.inc)
+
+struct HeadsShape {
+  int M, D, A, K;
+  bool composite;
+  lstm_input::RowInputs rows;
+};
+
+// Everything the kernels index by: x [M, D] bf16; policy.weight [A, K] and
+// baseline.weight [1, K], one dtype (fp32 or bf16), contiguous; reward and
+// prev_action [M] or both absent. Dense: K = D in {128, 256, 512}. Composite:
+// D = 256, K = 257 + A.
+static HeadsShape checkHeads(const at::Tensor& x, const at::Tensor& Wp, const at::Tensor& Wb,
+                             const c10::optional<at::Tensor>& reward,
+                             const c10::optional<at::Tensor>& action, const char* who) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.scalar_type() == at::kBFloat16, who,
+              ": x must be a [M, D] bf16 CUDA tensor, got ", x.scalar_type(), " ", x.sizes());
+  TORCH_CHECK(x.size(0) >= 1 && x.size(0) <= (1 << 24), who, ": M must be 1 to 2^24 rows");
+  TORCH_CHECK(x.is_contiguous() && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, who,
+              ": x must be contiguous and 16-byte aligned");
+  for (const at::Tensor* w : {&Wp, &Wb})
+    TORCH_CHECK(w->is_cuda() && w->device() == x.device() && w->dim() == 2 && w->is_contiguous() &&
+                    (w->scalar_type() == at::kFloat || w->scalar_type() == at::kBFloat16),
+                who, ": the head weights must be contiguous 2-d fp32 or bf16 tensors on x's device");
+  TORCH_CHECK(Wp.scalar_type() == Wb.scalar_type(), who, ": the two weights must have one dtype");
+  TORCH_CHECK(Wb.size(0) == 1 && Wb.size(1) == Wp.size(1), who, ": baseline weight must be [1, ",
+              Wp.size(1), "], got ", Wb.sizes());
+  TORCH_CHECK(reward.has_value() == action.has_value(), who,
+              ": reward and prev_action come together or not at all");
+  HeadsShape s;
+  s.M = x.size(0);
+  s.composite = reward.has_value();
+  const int64_t D = x.size(1), A = Wp.size(0), K = Wp.size(1);
+  TORCH_CHECK(A >= 1 && A <= heads::kMaxActions, who, ": 1 to ", heads::kMaxActions,
+              " actions are served, policy weight ", Wp.sizes(), " has ", A);
+  if (s.composite) {
+    TORCH_CHECK(D == heads::kCompositeD && K == D + 1 + A, who, ": with reward and prev_action x ",
+                "must be [M, 256] and the weights [A, 257 + A] and [1, 257 + A], got x ", x.sizes(),
+                ", policy weight ", Wp.sizes());
+  } else {
+    TORCH_CHECK((D == 128 || D == 256 || D == 512) && K == D, who,
+                ": x must be [M, D] with D in 128, 256, 512 and the weights [A, D] and [1, D], ",
+                "got x ", x.sizes(), ", policy weight ", Wp.sizes());
+  }
+  s.D = D;
+  s.A = A;
+  s.K = K;
+  s.rows = lstm_input::RowInputs{nullptr, nullptr, 0, 0};
+  if (s.composite) {
+    for (const at::Tensor* t : {&*reward, &*action})
+      TORCH_CHECK(t->is_cuda() && t->device() == x.device() && t->dim() == 1 &&
+                      t->size(0) == s.M && t->is_contiguous(),
+                  who, ": reward and prev_action must be contiguous [M] tensors on x's device");
+    s.rows.reward = reward->data_ptr();
+    s.rows.action = action->data_ptr();
+    s.rows.rewardKind = lstmInputRealKind(*reward, who, "reward");
+    s.rows.actionKind = lstmInputIntKind(*action, who, "prev_action");
+  }
+  return s;
+}
+
+// More than 64 KB of dynamic LDS has to be allowed per kernel, once.
+template <typename F>
+static bool headsAllowLds(F* kernel) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                             heads::kLdsMax) == hipSuccess;
+}
+
+template <typename WT, int D, int WAVES>
+static void headsFwdLaunch(const HeadsShape& s, const at::Tensor& x, const at::Tensor& Wp,
+                           const at::Tensor& Wb, const at::Tensor& bp, const at::Tensor& bb,
+                           int biasKind, at::Tensor& logits, at::Tensor& baseline) {
+  auto kernel = heads::fwd_kernel<WT, D, WAVES>;
+  static const bool ldsAllowed = headsAllowLds(kernel);
+  TORCH_CHECK(ldsAllowed, "heads fwd: the runtime refused ", heads::kLdsMax, " bytes of LDS");
+  const int lds = heads::fwdLdsBytes(D, WAVES, s.A, s.composite);
+  hipLaunchKernelGGL(kernel, dim3((s.M + WAVES * 16 - 1) / (WAVES * 16)), dim3(WAVES * 64),
+                     (size_t)lds, c10::hip::getCurrentHIPStream(),
+                     reinterpret_cast<const lstm::bf16*>(x.data_ptr()), s.rows,
+                     reinterpret_cast<const WT*>(Wp.data_ptr()),
+                     reinterpret_cast<const WT*>(Wb.data_ptr()), bp.data_ptr(), bb.data_ptr(),
+                     biasKind, logits.data_ptr<float>(), baseline.data_ptr<float>(), s.M, s.A,
+                     s.composite ? 1 : 0);
+}
+
+// Calls f with (weight type tag, D) as compile-time values.
+template <typename F>
+static void headsDispatch(const HeadsShape& s, const at::Tensor& Wp, F&& f) {
+  auto onD = [&](auto wt) {
+    if (s.D == 128)
+      f(wt, std::integral_constant<int, 128>());
+    else if (s.D == 256)
+      f(wt, std::integral_constant<int, 256>());
+    else
+      f(wt, std::integral_constant<int, 512>());
+  };
+  if (Wp.scalar_type() == at::kFloat)
+    onD(float());
+  else
+    onD(lstm::bf16());
+}
+
+// Returns (policy_logits [M, A] fp32, baseline [M] fp32).
+std::vector<at::Tensor> heads_fwd(at::Tensor x, at::Tensor Wp, at::Tensor bp, at::Tensor Wb,
+                                  at::Tensor bb, c10::optional<at::Tensor> reward,
+                                  c10::optional<at::Tensor> action) {
+  const char* who = "heads fwd";
+  HeadsShape s = checkHeads(x, Wp, Wb, reward, action, who);
+  const int biasKind = lstmInputRealKind(bp, who, "policy bias");
+  checkLstmArg(bp, x, bp.scalar_type(), {s.A}, who, "policy bias");
+  checkLstmArg(bb, x, bp.scalar_type(), {1}, who, "baseline bias");
+  auto fopts = x.options().dtype(at::kFloat);
+  auto logits = at::empty({s.M, s.A}, fopts);
+  auto baseline = at::empty({s.M}, fopts);
+  headsDispatch(s, Wp, [&](auto wt, auto d) {
+    using WT = decltype(wt);
+    constexpr int D = decltype(d)::value;
+    if (s.M < 1024)
+      headsFwdLaunch<WT, D, 1>(s, x, Wp, Wb, bp, bb, biasKind, logits, baseline);
+    else
+      headsFwdLaunch<WT, D, 4>(s, x, Wp, Wb, bp, bb, biasKind, logits, baseline);
+  });
+  return {logits, baseline};
+}
+
+// Returns (d_x [M, D] bf16 or an undefined tensor, d policy.weight [A, K],
+// d policy.bias [A], d baseline.weight [1, K], d baseline.bias [1], all fp32).
+// Either incoming gradient may be absent: it then counts as zero.
+std::vector<at::Tensor> heads_bwd(c10::optional<at::Tensor> dLogits,
+                                  c10::optional<at::Tensor> dBaseline, at::Tensor x, at::Tensor Wp,
+                                  at::Tensor Wb, c10::optional<at::Tensor> reward,
+                                  c10::optional<at::Tensor> action, bool needX) {
+  const char* who = "heads bwd";
+  HeadsShape s = checkHeads(x, Wp, Wb, reward, action, who);
+  if (dLogits.has_value()) checkLstmArg(*dLogits, x, at::kFloat, {s.M, s.A}, who, "dlogits");
+  if (dBaseline.has_value()) checkLstmArg(*dBaseline, x, at::kFloat, {s.M}, who, "dbaseline");
+  auto stream = c10::hip::getCurrentHIPStream();
+  auto fopts = x.options().dtype(at::kFloat);
+  at::Tensor dx;
+  if (needX) dx = at::empty_like(x);
+  const int slabs = (s.M + heads::kSlab - 1) / heads::kSlab;
+  const int Npad = (s.A + 1 + 15) / 16 * 16;
+  const int CW = s.D + (s.composite ? (s.A + 15) / 16 * 16 : 0) + 2;
+  auto ws = at::empty({slabs, Npad, CW}, fopts);
+  auto dWp = at::empty({s.A, s.K}, fopts);
+  auto dbp = at::empty({s.A}, fopts);
+  auto dWb = at::empty({1, s.K}, fopts);
+  auto dbb = at::empty({1}, fopts);
+  headsDispatch(s, Wp, [&](auto wt, auto d) {
+    using WT = decltype(wt);
+    constexpr int D = decltype(d)::value;
+    auto kernel = heads::bwd_kernel<WT, D>;
+    static const bool ldsAllowed = headsAllowLds(kernel);
+    TORCH_CHECK(ldsAllowed, "heads bwd: the runtime refused ", heads::kLdsMax, " bytes of LDS");
+    const int lds = heads::bwdLdsBytes(D, s.A, s.composite);
+    hipLaunchKernelGGL(kernel, dim3(slabs), dim3(heads::kBwdThreads), (size_t)lds, stream,
+                       dLogits.has_value() ? dLogits->data_ptr<float>() : nullptr,
+                       dBaseline.has_value() ? dBaseline->data_ptr<float>() : nullptr,
+                       reinterpret_cast<const lstm::bf16*>(x.data_ptr()), s.rows,
+                       reinterpret_cast<const WT*>(Wp.data_ptr()),
+                       reinterpret_cast<const WT*>(Wb.data_ptr()),
+                       needX ? reinterpret_cast<lstm::bf16*>(dx.data_ptr()) : nullptr,
+                       ws.data_ptr<float>(), s.M, s.A, s.composite ? 1 : 0);
+  });
+  const int outs = (s.A + 1) * (s.K + 1);
+  hipLaunchKernelGGL(heads::wgrad_reduce_kernel,
+                     dim3((outs + heads::kBwdThreads - 1) / heads::kBwdThreads),
+                     dim3(heads::kBwdThreads), 0, stream, ws.data_ptr<float>(),
+                     dWp.data_ptr<float>(), dbp.data_ptr<float>(), dWb.data_ptr<float>(),
+                     dbb.data_ptr<float>(), slabs, s.A, s.K, s.D, Npad, CW);
+  return {dx, dWp, dbp, dWb, dbb};
 }
 
 // ---- fused trunk FC (fc.hip.inc)
@@ -1740,6 +1915,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_input_bwd", &lstm_input_bwd,
         "fused LSTM input projection bwd: d_feat, dW_ih and the bias gradient, deterministic");
   m.attr("LSTM_INPUT_MAX_ACTIONS") = lstm_input::kMaxActions;  // widest action set served
+  m.def("heads_fwd", &heads_fwd,
+        "policy and baseline heads in one MFMA launch, fp32 outputs from nn.Linear's own weights");
+  m.def("heads_bwd", &heads_bwd,
+        "heads backward: d_x and the four parameter gradients, two launches, no atomics");
+  m.attr("HEADS_MAX_ACTIONS") = heads::kMaxActions;  // widest action set served
   m.def("trunk_fc_fwd", &trunk_fc_fwd,
         "fused trunk FC: NHWC x -> relu(fc), W read in place, split-K MFMA (gfx950)");
   m.def("trunk_fc_bwd", &trunk_fc_bwd,

@@ -94,6 +94,11 @@ class ImpalaConfig:
     #   MFMA forward, masked dgrad, weight gradient in nn.Linear's order), in
     #   the actor's and the learner's forward alike.
     #   MOOLIB_AMD_FUSED_TRUNK_FC=1 switches it on.
+    fused_heads: bool = False  # the policy and baseline heads as one op on
+    #   their own weights (ops.heads.policy_value_heads: one MFMA launch with
+    #   fp32 outputs, two in the backward; without an LSTM the reward and
+    #   prev_action go in too and one_hot, clamp and cat never run).
+    #   MOOLIB_AMD_FUSED_HEADS=1 switches it on.
     graph_learner: bool = False  # hipGraph-capture the learner fwd+bwd.
     #   OFF by default: replays of the captured learner (autograd backward
     #   incl. MIOpen bwd-weight convs) intermittently fault on ROCm 7.0
@@ -271,6 +276,8 @@ class ImpalaPeer:
             cfg.fused_sampling = True
         if os.environ.get("MOOLIB_AMD_FUSED_TRUNK_FC", "0") == "1":
             cfg.fused_trunk_fc = True
+        if os.environ.get("MOOLIB_AMD_FUSED_HEADS", "0") == "1":
+            cfg.fused_heads = True
         if cfg.fused_optimizer:
             # optim.FlatAdam, built by _build_fused_optimizer once the flat
             # buffers exist
@@ -377,6 +384,8 @@ class ImpalaPeer:
         for m in {id(m): m for m in (self.model, self.fwd_model)}.values():
             if hasattr(m, "fused_trunk_fc"):
                 m.fused_trunk_fc = cfg.fused_trunk_fc
+            if hasattr(m, "fused_heads"):
+                m.fused_heads = cfg.fused_heads
         if cfg.fused_optimizer:
             self._build_fused_optimizer()
         self.env_states = [

@@ -31,6 +31,8 @@ call (the MOOLIB_AMD_* switches may change between two forwards):
 | core input | otherwise | one_hot, clamp, cat; on the fused-scan branch `F.linear` over all T |
 | core recurrent weight | `fused_core_recurrent=True` and the fused-scan branch is taken | `fused_lstm_scan(..., native_whh=True)`: one pack launch for `weight_hh_l0`, `lstm_ops.recurrent_weight_grad` for its gradient |
 | core recurrent weight | otherwise | bf16 cast, transpose and `pack_mfma_b` in torch; cat, mask multiply, fp32 casts and an fp32 GEMM in the backward |
+| heads | `fused_heads=True`, the head input (`core_output` with an LSTM, `relu(fc)` without) is CUDA bf16 and `heads_ops.heads_available` | `heads_ops.policy_value_heads` (hip/heads.hip.inc) on `policy`'s and `baseline`'s own weights: one launch, fp32 outputs from the fp32 accumulators; without an LSTM it takes the reward and `prev_action` too, and one_hot, clamp and cat never run |
+| heads | otherwise | `self.policy(core_output).float()`, `self.baseline(core_output).float()` |
 
 A bias-free conv is the MFMA kernel when `conv3x3.runs_on_mfma`, else
 F.conv2d (MIOpen). tests/test_trunk_routes.py pins the launches of each row.
@@ -45,6 +47,7 @@ from moolib_amd.ops import act as act_ops
 from moolib_amd.ops import conv3x3 as c3
 from moolib_amd.ops import fc as fc_ops
 from moolib_amd.ops import fused_bias
+from moolib_amd.ops import heads as heads_ops
 from moolib_amd.ops import lstm as lstm_ops
 from moolib_amd.ops.fused_bias import bias_add2, bias_relu
 from moolib_amd.ops.pool import maxpool3x3s2
@@ -143,7 +146,7 @@ class ConvSection(nn.Module):
 class AtariNet(nn.Module):
     def __init__(self, num_actions=18, input_channels=4, use_lstm=False, lstm_size=256,
                  fused_core_input=False, fused_core_recurrent=False,
-                 fused_actor_sections=False, fused_trunk_fc=False):
+                 fused_actor_sections=False, fused_trunk_fc=False, fused_heads=False):
         super().__init__()
         self.num_actions = num_actions
         self.use_lstm = use_lstm
@@ -152,6 +155,7 @@ class AtariNet(nn.Module):
         self.fused_core_recurrent = fused_core_recurrent
         self.fused_actor_sections = fused_actor_sections
         self.fused_trunk_fc = fused_trunk_fc
+        self.fused_heads = fused_heads
 
         chans = [16, 32, 32]
         sections = []
@@ -218,6 +222,16 @@ class AtariNet(nn.Module):
                 x = x.contiguous(memory_format=torch.channels_last)
         return sec0(x, fused)
 
+    def _heads_route(self, head_in, composite):
+        """Whether the heads run as ops.heads.policy_value_heads on `head_in`."""
+        return (
+            self.fused_heads
+            and head_in.is_cuda
+            and head_in.dtype == torch.bfloat16
+            and heads_ops.heads_available(head_in.size(1), self.num_actions, composite,
+                                          head_in.device)
+        )
+
     def forward(self, inputs, core_state=None):
         x = inputs["state"]
         reward = inputs["reward"]
@@ -246,8 +260,13 @@ class AtariNet(nn.Module):
             and lstm_ops.available(self.core.hidden_size, x.device)
             and (torch.is_autocast_enabled() or x.dtype == torch.bfloat16)
         )
+        # without an LSTM the fused heads read relu(fc), reward and prev_action
+        # themselves: the core input is never built
+        composite_heads = not self.use_lstm and self._heads_route(x, True)
         Xg = None
-        if (
+        if composite_heads:
+            core_input = None
+        elif (
             fused_scan
             and self.fused_core_input
             and x.dtype == torch.bfloat16
@@ -305,8 +324,19 @@ class AtariNet(nn.Module):
         else:
             core_output = core_input
 
-        policy_logits = self.policy(core_output).float()
-        baseline = self.baseline(core_output).float()
+        if composite_heads:
+            policy_logits, baseline = heads_ops.policy_value_heads(
+                x, self.policy.weight, self.policy.bias, self.baseline.weight, self.baseline.bias,
+                reward.reshape(T * B), inputs["prev_action"].reshape(T * B),
+            )
+        elif self.use_lstm and self._heads_route(core_output, False):
+            policy_logits, baseline = heads_ops.policy_value_heads(
+                core_output, self.policy.weight, self.policy.bias,
+                self.baseline.weight, self.baseline.bias,
+            )
+        else:
+            policy_logits = self.policy(core_output).float()
+            baseline = self.baseline(core_output).float()
         out = dict(
             policy_logits=policy_logits.view(T, B, self.num_actions),
             baseline=baseline.view(T, B),
@@ -332,11 +362,11 @@ class AtariNet(nn.Module):
 
 def create_model(num_actions=18, use_lstm=False, device="cpu", lstm_size=256,
                  fused_core_input=False, fused_core_recurrent=False,
-                 fused_actor_sections=False, fused_trunk_fc=False):
+                 fused_actor_sections=False, fused_trunk_fc=False, fused_heads=False):
     model = AtariNet(num_actions=num_actions, use_lstm=use_lstm, lstm_size=lstm_size,
                      fused_core_input=fused_core_input,
                      fused_core_recurrent=fused_core_recurrent,
                      fused_actor_sections=fused_actor_sections,
-                     fused_trunk_fc=fused_trunk_fc)
+                     fused_trunk_fc=fused_trunk_fc, fused_heads=fused_heads)
     model.to(device)
     return model
