@@ -410,6 +410,7 @@ __global__ __launch_bounds__(256) void conv1_u8_nhwc_kernel(const uint8_t* __res
 #include "conv3x3.hip.inc"
 #include "actor_section.hip.inc"
 #include "wgrad3x3.hip.inc"
+#include "wgrad3x3_splitk.hip.inc"
 #include "lstm.hip.inc"
 #include "lstm_wide.hip.inc"
 #include "lstm_input.hip.inc"
@@ -1904,6 +1905,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("ACTOR_SECTION_LDS_MAX") = actor_section::kLdsMax;
   m.def("wgrad3x3_nhwc", &wgrad3x3_nhwc,
         "3x3/s1/p1 conv weight gradient on MFMA (row-slab LDS staging, gfx950)");
+  m.def("wgrad3x3_splitk", &wgrad3x3_splitk,
+        "3x3/s1/p1 conv weight gradient, deterministic split-K on MFMA: (dW fp32 [K, c_real, 3, 3], "
+        "db fp32 [K] or empty); no atomics",
+        py::arg("x"), py::arg("dy"), py::arg("c_real"), py::arg("want_db"));
+  m.def("wgrad3x3_splitk_rows", &wgrad3x3_splitk_rows,
+        "output rows per slab wgrad3x3_splitk uses for (C, K, W); 0 when W is too wide",
+        py::arg("C"), py::arg("K"), py::arg("W"));
   m.def("lstm_fused_fwd", &lstm_fused_fwd, "fused masked LSTM sequence scan fwd (MFMA, gfx950)");
   m.def("lstm_fused_bwd", &lstm_fused_bwd, "fused masked LSTM sequence scan bwd (MFMA, gfx950)");
   m.def("lstm_wide_fwd", &lstm_wide_fwd,

@@ -25,6 +25,7 @@ call (the MOOLIB_AMD_* switches may change between two forwards):
 | section after its conv | `fused_actor_sections=True`, no grad, `fused_bias.available` and `conv3x3.actor_section_available` (MFMA blocks, two pooled images fit LDS, not NO_ACTOR_SECTION) | `conv3x3.actor_section`: pool and both blocks in one launch with the image resident in LDS, the same values as the rows below; the trunk's trailing relu rides in the last section's launch |
 | block in `forward_fused` | no grad and `conv3x3.runs_on_mfma` | two fused MFMA conv launches |
 | block in `forward_fused` | otherwise | `bias_relu`/relu, conv, `bias_relu`, conv, `bias_add2` |
+| conv weight gradient | MFMA conv under autograd (`conv3x3.conv3x3_autograd`, `conv1_u8_autograd`) | MOOLIB_AMD_WGRAD_KERNEL unset or empty: `aten.convolution_backward` (MIOpen wrw), the first conv `wgrad3x3_nhwc` + `channel_sum_fp32`; any other value but "2": `wgrad3x3_nhwc` (atomic fold) + a torch permute; "2": `conv3x3.wgrad` (hip/wgrad3x3_splitk.hip.inc), dW in `nn.Conv2d`'s order and the first conv's db from one deterministic split-K launch pair |
 | trunk FC | `fused_trunk_fc=True`, the tensor entering the last section is CUDA with bf16 compute and `fc_ops.trunk_fc_available` | the last section runs with `relu_out=False`; `fc_ops.trunk_fc(x, fc.weight, fc.bias, relu_in=True)` (hip/fc.hip.inc) is the trunk's trailing relu, the flatten, `fc` and its relu on the channels_last tensor and `fc`'s own weight: no layout copy, weight cast or vendor GEMM, in grad and no-grad mode alike |
 | trunk FC | otherwise | the last section applies the relu; `reshape` (a copy to NCHW order), `self.fc`, `F.relu` |
 | core input | `fused_core_input=True`, the fused-scan branch is taken and `lstm_ops.core_input_available` | `lstm_ops.core_input_projection` on `relu(fc(x))`, reward, prev_action and the core's own `weight_ih_l0` and biases: no one_hot, clamp, cat or `F.linear` |

@@ -6,8 +6,10 @@ bias / bias+relu / bias+residual epilogue fused into the store. An IMPALA
 residual block (reference examples/atari/models.py:30-42) becomes two
 kernel launches on the actor. The learner uses `conv3x3_autograd`
 (forward + input-gradient on the same kernel; weight gradient via MIOpen
-wrw by default, our wgrad3x3 kernel opt-in); `conv1_u8_autograd` is the
-uint8 first layer of both. `runs_on_mfma` is the one place that decides
+wrw by default, MOOLIB_AMD_WGRAD_KERNEL=1 our row-slab wgrad3x3 kernel,
+=2 the deterministic split-K kernel of hip/wgrad3x3_splitk.hip.inc, which
+also returns the bias sum; `wgrad` prepares its operands);
+`conv1_u8_autograd` is the uint8 first layer of both. `runs_on_mfma` is the one place that decides
 whether a conv takes the kernel, `packed` the one cache of packed weights
 (kinds in PACKERS), refreshed by `repack`. `actor_section` wraps
 hip/actor_section.hip.inc: pool and both residual blocks of a trunk section
@@ -173,11 +175,29 @@ def repack(module):
                 entry[0] = m.weight._version
 
 
+def splitk_wgrad():
+    """Is the split-K weight-gradient kernel selected? Read per call; any
+    value of MOOLIB_AMD_WGRAD_KERNEL other than "2" keeps the older routes."""
+    return os.environ.get("MOOLIB_AMD_WGRAD_KERNEL") == "2"
+
+
+def wgrad(x, dy, c_real=None, want_db=False):
+    """(dW fp32 [K, c_real, 3, 3], db fp32 [K] or empty) of a 3x3/s1/p1 conv
+    from its input x [N,C,H,W] and output gradient dy [N,K,H,W], on the
+    split-K MFMA kernel: fixed summation order, no atomics. Channels of x
+    from `c_real` on (zero padding of the first conv) get no gradient."""
+    to = lambda t: t.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    return _k().wgrad3x3_splitk(
+        to(x), to(dy), x.shape[1] if c_real is None else c_real, want_db
+    )
+
+
 class _Conv3x3Fn(torch.autograd.Function):
     """3x3/s1/p1 NHWC conv with fwd AND dgrad on the MFMA kernel.
 
     Weight gradient defaults to aten.convolution_backward (MIOpen wrw
-    igemm); MOOLIB_AMD_WGRAD_KERNEL=1 switches to our wgrad3x3 kernel.
+    igemm); MOOLIB_AMD_WGRAD_KERNEL=1 switches to our wgrad3x3 kernel,
+    =2 to the split-K kernel (`wgrad`), whose result is bit-reproducible.
     Drop-in for F.conv2d(x, w, None, padding=1) on supported shapes."""
 
     @staticmethod
@@ -200,7 +220,9 @@ class _Conv3x3Fn(torch.autograd.Function):
             if dx.dtype != ctx.x_dtype:
                 dx = dx.to(ctx.x_dtype)
         if ctx.needs_input_grad[1]:
-            if os.environ.get("MOOLIB_AMD_WGRAD_KERNEL"):
+            if splitk_wgrad():
+                dw = wgrad(x, dy, w.shape[1])[0]
+            elif os.environ.get("MOOLIB_AMD_WGRAD_KERNEL"):
                 # Opt-in: the row-slab wgrad kernel is numerics-correct
                 # (TestWgradKernel) and, after the accumulator-scratch fix,
                 # within 1.1-1.25x of MIOpen's igemm_wrw at IMPALA learner
@@ -246,7 +268,8 @@ def _conv1_u8(x_u8, conv, scale):
 
 class _Conv1U8Fn(torch.autograd.Function):
     """_conv1_u8 under autograd: dW comes from our wgrad kernel on the
-    saved padded activation, db is a sum. No MIOpen anywhere in the layer
+    saved padded activation, db is a sum (MOOLIB_AMD_WGRAD_KERNEL=2: both
+    from the split-K kernel, one launch pair). No MIOpen anywhere in the layer
     (frames never need an input gradient)."""
 
     @staticmethod
@@ -261,6 +284,10 @@ class _Conv1U8Fn(torch.autograd.Function):
         k = _k()
         dyb = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         K, C = w.shape[0], w.shape[1]
+        if splitk_wgrad():
+            # dW and db from one pass over dy
+            dw, db = wgrad(xb8, dyb, C, True)
+            return None, dw.to(w.dtype), db.to(w.dtype), None, None
         g = k.wgrad3x3_nhwc(xb8, dyb)[: 9 * 8]
         dw = g.view(3, 3, 8, K)[:, :, :C].permute(3, 2, 0, 1).to(w.dtype)
         # small-grid NHWC channel sum (hip/kernels.hip channel_sum_kernel)
